@@ -16,6 +16,12 @@ candidates at every N — per-GPU work constant (weak scaling), hipGraphs
 stay enabled at all N (no in-step collectives), and the winner broadcasts
 over RCCL/xGMI at each iteration end. --placement replication selects
 synchronous data-parallel instead (flat per-candidate gradient buckets).
+
+A plain run sets up, warms up, times --steps iterations and prints the
+result line. --dump-outputs DIR additionally saves what the last timed
+iteration produced as .npy files (inputs and seeds are fixed, so two builds
+can be compared array for array); --full adds the checks the headline does
+not need (final ensemble eval accuracy).
 """
 
 import argparse
@@ -58,7 +64,64 @@ def parse_args():
     p.add_argument("--per-iter-json", default=None,
                    help="write a per-iteration wall-clock curve (ms vs "
                         "ensemble size + winner arch) to this path, rank 0")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed "
+                        "iteration produced (the winner's frozen member "
+                        "weights, the ensemble's mixture state, the "
+                        "selected candidate indices) as DIR/<name>.npy, "
+                        "rank 0")
+    p.add_argument("--full", action="store_true",
+                   help="also run the checks that the headline figure does "
+                        "not need: the final ensemble's eval accuracy "
+                        "(config.final_ensemble_accuracy)")
     return p.parse_args()
+
+
+# --dump-outputs budget: 12M float32 elements (48 MB) over all arrays.
+_DUMP_MAX_ELEMS = 12 * 1024 * 1024
+
+
+def _dump_outputs(est, out_dir):
+    """Writes the arrays a caller of the timed path receives from its last
+    iteration: the state dict of every member that iteration froze, the
+    winning ensemble's mixture state and the per-iteration selected indices.
+    Arrays beyond the size budget are cut to a fixed, seeded sample of their
+    flattened elements (same indices every run)."""
+    import re
+
+    import numpy as np
+
+    t = est.iteration_number - 1
+    arrays = {}
+    for key in sorted(est._frozen_states):
+        sd = est._frozen_states[key]
+        if sd is None or not key.startswith(est._frozen_key(t, "")):
+            continue
+        for k in sorted(sd):
+            arrays["member.%s.%s" % (key, k)] = sd[k]
+    for k in sorted(est._best_ensemble_state or {}):
+        arrays["ensemble.%s" % k] = est._best_ensemble_state[k]
+    arrays = {k: v.detach().cpu().to(torch.float32).numpy()
+              for k, v in arrays.items() if torch.is_tensor(v)}
+    arrays["selected_indices"] = np.asarray(est._replay_indices,
+                                            dtype=np.float64)
+
+    # Split the budget smallest-first: small arrays go out whole and what
+    # they leave over is shared among the larger ones.
+    keep = {}
+    remaining = _DUMP_MAX_ELEMS
+    by_size = sorted(arrays, key=lambda k: (arrays[k].size, k))
+    for n_left, name in zip(range(len(by_size), 0, -1), by_size):
+        keep[name] = min(arrays[name].size, remaining // n_left)
+        remaining -= keep[name]
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if keep[name] < a.size:
+            idx = np.sort(np.random.default_rng(i).choice(
+                a.size, size=keep[name], replace=False))
+            a = a.reshape(-1)[idx]
+        fname = re.sub(r"[^A-Za-z0-9_.-]+", "_", name) + ".npy"
+        np.save(os.path.join(out_dir, fname), np.ascontiguousarray(a))
 
 
 def _self_launch(args):
@@ -237,8 +300,13 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    res = est.evaluate(eval_input_fn, steps=args.eval_batches)
-    final_acc = float(res.get("accuracy", float("nan")))
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(est, args.dump_outputs)
+
+    final_acc = None
+    if args.full:
+        res = est.evaluate(eval_input_fn, steps=args.eval_batches)
+        final_acc = float(res.get("accuracy", float("nan")))
 
     iters_per_hour = args.steps / elapsed * 3600.0
     if rank == 0:
@@ -268,10 +336,11 @@ def main():
                 "parallelism": ("dp%d" % world
                                 if args.placement == "replication" else
                                 "round_robin%d" % world),
-                "final_ensemble_accuracy": final_acc,
                 "final_ensemble_size": est.iteration_number,
             },
         }
+        if args.full:
+            out["config"]["final_ensemble_accuracy"] = final_acc
         print(json.dumps(out))
         if args.per_iter_json:
             with open(args.per_iter_json, "w") as f:

@@ -1,5 +1,7 @@
 """Compare two bench runs for determinism: winner sequence, ensemble
-sizes, and final ensemble accuracy must match exactly.
+sizes, and final ensemble accuracy must match exactly. Both runs are
+`bench.py --full --per-iter-json <iters.json>` (the accuracy is only
+measured under --full).
 
 python benchmarks/compare_runs.py runA.log runA_iters.json \
                                   runB.log runB_iters.json

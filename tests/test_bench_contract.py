@@ -22,7 +22,7 @@ def _free_port():
 
 def test_bench_single_process_cpu(tmp_path):
     out = subprocess.run(
-        [sys.executable, os.path.join(REPO, "bench.py"), "--cpu",
+        [sys.executable, os.path.join(REPO, "bench.py"), "--cpu", "--full",
          "--steps", "1", "--warmup", "0", "--batch", "64", "--hidden", "32",
          "--train-steps-per-iter", "3", "--eval-batches", "2"],
         capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
@@ -35,6 +35,49 @@ def test_bench_single_process_cpu(tmp_path):
     assert d["scaling"] == "weak"
     assert d["dtype"] == "fp32"  # --cpu debug mode; bf16 on GPU
     assert "final_ensemble_accuracy" in d["config"]
+    assert 0.0 <= d["config"]["final_ensemble_accuracy"] <= 1.0
+
+
+def _plain_cpu_run(tmp_path, dump_dir):
+    out = subprocess.run(
+        [sys.executable, os.path.join(REPO, "bench.py"), "--cpu",
+         "--steps", "2", "--warmup", "1", "--batch", "64", "--hidden", "32",
+         "--train-steps-per-iter", "3", "--eval-batches", "2",
+         "--dump-outputs", str(dump_dir)],
+        capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps iterations, skips the
+    final-accuracy evaluation, and --dump-outputs writes the last
+    iteration's arrays — identical from run to run."""
+    import numpy as np
+
+    d = _plain_cpu_run(tmp_path, tmp_path / "a")
+    assert d["steps"] == 2 and d["warmup"] == 1
+    assert d["config"]["final_ensemble_size"] == 3  # warmup + steps
+    assert d["ms_per_step"] > 0
+    assert abs(d["value"] - 3600.0 * 1000.0 / d["ms_per_step"]) < 1e-6 * d[
+        "value"]
+    assert "final_ensemble_accuracy" not in d["config"]
+
+    _plain_cpu_run(tmp_path, tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert "selected_indices.npy" in names
+    assert any(n.startswith("member.t2_") for n in names)
+    assert any(n.startswith("ensemble.") for n in names)
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / n))
+        total += a.nbytes
+    assert total <= 64 * 1024 * 1024
+    assert len(np.load(tmp_path / "a" / "selected_indices.npy")) == 3
 
 
 def test_bench_torchrun_two_ranks_cpu(tmp_path):
