@@ -81,6 +81,17 @@ void relu_bwd_colsum(const at::Tensor& dy, const at::Tensor& y,
                      at::Tensor& dz, at::Tensor& db, double scale);
 void multi_copy_bf16(const std::vector<at::Tensor>& srcs,
                      const std::vector<at::Tensor>& dsts);
+void cell_combine_fwd(const std::vector<at::Tensor>& lefts,
+                      const std::vector<at::Tensor>& rights,
+                      const std::vector<at::Tensor>& scales_l,
+                      const std::vector<at::Tensor>& scales_r, at::Tensor& out,
+                      int64_t block_offset);
+void cell_combine_bwd(const at::Tensor& dy,
+                      const std::vector<at::Tensor>& scales_l,
+                      const std::vector<at::Tensor>& scales_r,
+                      const std::vector<c10::optional<at::Tensor>>& dlefts,
+                      const std::vector<c10::optional<at::Tensor>>& drights,
+                      int64_t block_offset);
 void colsum_bf16(const at::Tensor& x, at::Tensor& out, int64_t accum);
 void binary_histogram(const at::Tensor& scores, const at::Tensor& labels,
                       at::Tensor& hist);
@@ -151,6 +162,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_bwd_colsum", &relu_bwd_colsum, py::arg("dy"), py::arg("y"),
         py::arg("dz"), py::arg("db"), py::arg("scale") = 1.0);
   m.def("multi_copy_bf16", &multi_copy_bf16);
+  m.def("cell_combine_fwd", &cell_combine_fwd,
+        "fused drop-path scale + add + channel concat of up to 8 block pairs",
+        py::arg("lefts"), py::arg("rights"), py::arg("scales_l"),
+        py::arg("scales_r"), py::arg("out"), py::arg("block_offset") = 0);
+  m.def("cell_combine_bwd", &cell_combine_bwd, py::arg("dy"),
+        py::arg("scales_l"), py::arg("scales_r"), py::arg("dlefts"),
+        py::arg("drights"), py::arg("block_offset") = 0);
   m.def("colsum_bf16", &colsum_bf16, py::arg("x"), py::arg("out"),
         py::arg("accum") = 0);
   m.def("argmax_correct", &argmax_correct);

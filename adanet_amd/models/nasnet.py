@@ -4,10 +4,15 @@ MI355X-native re-implementation of the structures the reference ports from
 slim (research/improve_nas/trainer/nasnet.py:250-530 build_nasnet_cifar,
 nasnet_utils.py: factorized_reduction :94, drop_path :137,
 _stacked_separable_conv :182, NasNetABaseCell :318) — written from the
-NASNet-A paper genotype, not translated: convolutions/pooling run through
-torch (MIOpen on ROCm — library conv, the sanctioned path for non-headline
-ops), batch-norm statistics compute in fp32 under bf16 activations, and
-the classifier head + optimizers use the adanet_amd HIP kernels.
+NASNet-A paper genotype, not translated. On the GPU in bf16 every op on the
+cell path runs on the in-tree gfx950 kernels: depthwise, pointwise (batched
+MFMA GEMM) and NxN convolutions, 3x3 pooling, BatchNorm with fp32 statistics
+under bf16 activations, and the fused cell combine (drop-path scale, add
+and channel concat in one launch, ops/combine.py); with filter counts that
+are multiples of 32 no MIOpen kernel is left on it (other counts take
+torch's conv for the pointwise/NxN convolutions, ops/conv.py). The
+classifier head and optimizers use the adanet_amd HIP kernels as well; on
+CPU the same modules fall back to plain torch.
 """
 
 from __future__ import annotations
@@ -19,6 +24,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from adanet_amd.ops import combine
 from adanet_amd.ops.linear import HipLinear
 
 
@@ -36,16 +42,23 @@ class BNfp32(nn.Module):
         return self.bn(x)
 
 
-def drop_path(x, keep_prob: float, training: bool):
-    """Per-sample stochastic branch drop (reference nasnet_utils.py:137)."""
+def drop_path_scale(x, keep_prob: float, training: bool):
+    """The per-sample [B,1,1,1] drop-path factor for ``x`` (0 or 1/keep),
+    drawn but not applied; None when drop-path is inactive."""
     if not training or keep_prob >= 1.0:
-        return x
+        return None
     # Fold 1/keep into the tiny [B,1,1,1] mask so the full-size tensor is
     # touched ONCE (x * mask / keep was two full-tensor kernels fwd and two
     # in backward — the broadcast mul soup was 4%+ of the NASNet step).
     mask = (torch.rand(x.shape[0], 1, 1, 1, device=x.device)
             < keep_prob).to(x.dtype)
-    return x * (mask * (1.0 / keep_prob))
+    return mask * (1.0 / keep_prob)
+
+
+def drop_path(x, keep_prob: float, training: bool):
+    """Per-sample stochastic branch drop (reference nasnet_utils.py:137)."""
+    scale = drop_path_scale(x, keep_prob, training)
+    return x if scale is None else x * scale
 
 
 class SepConv(nn.Module):
@@ -202,17 +215,59 @@ class NasNetACell(nn.Module):
             self.ops_right.append(_make_op(op_r, filters, filters, stride_r))
             self.idx.append((in_l, in_r))
         self.out_channels = filters * len(genotype)
+        # Blocks whose output a later block reads. Each is combined on its
+        # own so that its state is a dense tensor the conv/pool kernels take
+        # as is; every run of other blocks shares one fused combine launch.
+        # Normal cell: no block is read again -> one launch IS the cell
+        # output. Reduction cell: [0], [1], [2, 3, 4] and one cat of three.
+        self._read_later = {j - 2 for pair in self.idx for j in pair
+                            if j >= 2}
 
     def forward(self, h_prev_prev, h_prev):
         states = [self.pre0(h_prev_prev), self.pre1(h_prev)]
+        pieces = []
+        pending = ([], [], [], [])  # lefts, rights, scales_l, scales_r
+
+        def flush():
+            if pending[0]:
+                scaled = pending[2][0] is not None
+                pieces.append(combine.cell_combine(
+                    pending[0], pending[1],
+                    pending[2] if scaled else None,
+                    pending[3] if scaled else None))
+                for p in pending:
+                    del p[:]
+
         for i, (op_l, op_r) in enumerate(zip(self.ops_left, self.ops_right)):
             in_l, in_r = self.idx[i]
             left = op_l(states[in_l])
             right = op_r(states[in_r])
-            left = drop_path(left, self.drop_path_keep, self.training)
-            right = drop_path(right, self.drop_path_keep, self.training)
-            states.append(left + right)
-        return torch.cat(states[2:], dim=1)
+            # An `id` branch returns the state itself. Give it a node of its
+            # own (a free alias, no kernel) at the point where the unfused
+            # multiply/add stood, so autograd adds this branch's gradient
+            # into the state's in the same order as before the fusion —
+            # bf16 sums of three or more terms depend on that order.
+            if left is states[in_l]:
+                left = left.view_as(left)
+            if right is states[in_r]:
+                right = right.view_as(right)
+            # Same torch.rand calls in the same order as drop_path(left),
+            # drop_path(right): a seeded run draws the same masks.
+            scale_l = drop_path_scale(left, self.drop_path_keep,
+                                      self.training)
+            scale_r = drop_path_scale(right, self.drop_path_keep,
+                                      self.training)
+            if i in self._read_later:
+                flush()
+            for p, t in zip(pending, (left, right, scale_l, scale_r)):
+                p.append(t)
+            if i in self._read_later:
+                flush()
+                states.append(pieces[-1])
+            else:
+                states.append(None)  # never read (see _read_later)
+        flush()
+        return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
 
 
 class NasNetCIFAR(nn.Module):
