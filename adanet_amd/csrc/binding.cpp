@@ -92,6 +92,13 @@ void cell_combine_bwd(const at::Tensor& dy,
                       const std::vector<c10::optional<at::Tensor>>& dlefts,
                       const std::vector<c10::optional<at::Tensor>>& drights,
                       int64_t block_offset);
+void augment_draw(const at::Tensor& labels, at::Tensor& params,
+                  at::Tensor& labels_out, uint64_t seed, int64_t step,
+                  int64_t rank, int64_t world, int64_t N, int64_t pad,
+                  int64_t H, int64_t W, bool augment);
+void augment_apply(const at::Tensor& data, const at::Tensor& params,
+                   const at::Tensor& scale, const at::Tensor& shift,
+                   at::Tensor& out, int64_t pad, int64_t cutout_pad);
 void colsum_bf16(const at::Tensor& x, at::Tensor& out, int64_t accum);
 void binary_histogram(const at::Tensor& scores, const at::Tensor& labels,
                       at::Tensor& hist);
@@ -169,6 +176,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cell_combine_bwd", &cell_combine_bwd, py::arg("dy"),
         py::arg("scales_l"), py::arg("scales_r"), py::arg("dlefts"),
         py::arg("drights"), py::arg("block_offset") = 0);
+  m.def("augment_draw", &augment_draw,
+        "per-sample (index, oy, ox, flip, cy, cx) from the counter RNG, plus "
+        "the gathered labels",
+        py::arg("labels"), py::arg("params"), py::arg("labels_out"),
+        py::arg("seed"), py::arg("step"), py::arg("rank"), py::arg("world"),
+        py::arg("N"), py::arg("pad"), py::arg("H"), py::arg("W"),
+        py::arg("augment") = true);
+  m.def("augment_apply", &augment_apply,
+        "fused gather + pad-crop + flip + cutout + normalise + bf16 cast",
+        py::arg("data"), py::arg("params"), py::arg("scale"),
+        py::arg("shift"), py::arg("out"), py::arg("pad"),
+        py::arg("cutout_pad"));
   m.def("colsum_bf16", &colsum_bf16, py::arg("x"), py::arg("out"),
         py::arg("accum") = 0);
   m.def("argmax_correct", &argmax_correct);

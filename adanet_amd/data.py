@@ -10,6 +10,11 @@ wraps any ``input_fn`` (an iterable of (features, labels) CPU batches) with:
 
 Synthetic/resident datasets (bench.py) bypass this entirely — tensors are
 already in HBM. On CPU the wrapper is pass-through.
+
+``DeviceImageLoader`` is the other shape for image sets that fit in HBM: the
+dataset is uploaded once as uint8 and every batch is drawn, augmented,
+normalised and cast on the device (csrc/augment.hip), with no host pixel work
+at all.
 """
 
 from __future__ import annotations
@@ -122,3 +127,133 @@ class _DeviceIterator(object):
         ev.wait(torch.cuda.current_stream(self._device))
         self._enqueue()
         return f, l
+
+
+class DeviceImageLoader(object):
+    """Device-resident image dataset with on-device augmentation.
+
+    ``images`` (uint8 or float32 ``[N, C, H, W]``) and ``labels`` (``[N]``)
+    are uploaded to ``device`` once, here. After that a training batch is two
+    kernel launches (``ops.augment.draw_params`` + ``augment_apply``): no
+    host pixel work, no pinned staging, no host-to-device copy. It is itself
+    a valid ``input_fn``: calling it returns a fresh iterator that starts at
+    ``start_step``.
+
+    Training mode yields an endless stream of ``(bf16 [B, C, H, W], int64
+    [B])``, sampled with replacement. Batch ``s`` is a pure function of
+    ``(seed, s, shard, data)``: equal loaders yield bit-identical batches
+    and ``start_step=k`` resumes the same stream at batch ``k``. ``shard =
+    (rank, world)`` gives each rank its own counters. ``augment=False``
+    still draws the indices but centres the crop, never flips and turns
+    cutout off.
+
+    Evaluation mode (``training=False``) visits every example once, in
+    order, unaugmented; the last batch may be short. Its feature tensors
+    carry ``adanet_cache_key = ("image-eval", id(loader), batch_index)`` so
+    the frozen-logit HBM cache applies; training batches carry none.
+
+    ``normalize``: ``"unit"`` maps uint8 to [-1, 1] (scale 2/255, shift -1;
+    pad and cutout pixels, written as 0, are then mid-grey); ``"none"`` maps
+    uint8 to [0, 1]; both leave float data as it is. A ``(mean, std)`` pair
+    of per-channel sequences gives ``(x - mean) / std`` with ``x`` in [0, 1]
+    for uint8 data.
+    """
+
+    def __init__(self, images, labels, batch_size: int, device,
+                 training: bool = True, augment: bool = True, pad: int = 4,
+                 cutout_pad: int = 8, normalize="unit", seed: int = 0,
+                 start_step: int = 0, shard: Tuple[int, int] = (0, 1)):
+        images = torch.as_tensor(images)
+        labels = torch.as_tensor(labels)
+        if images.dim() != 4 or images.dtype not in (torch.uint8,
+                                                     torch.float32):
+            raise ValueError("DeviceImageLoader: images must be uint8 or "
+                             "float32 [N, C, H, W] (got %s %s)"
+                             % (images.dtype, tuple(images.shape)))
+        n = images.shape[0]
+        if not (1 <= n < 2 ** 31):
+            raise ValueError("DeviceImageLoader: need 1 <= N < 2^31 images")
+        if labels.dim() != 1 or labels.shape[0] != n \
+                or labels.is_floating_point():
+            raise ValueError("DeviceImageLoader: labels must be N integers")
+        rank, world = (int(v) for v in shard)
+        if batch_size < 1 or pad < 0 or cutout_pad < 0 or start_step < 0 \
+                or world < 1 or not (0 <= rank < world):
+            raise ValueError("DeviceImageLoader: bad batch_size, pad, "
+                             "cutout_pad, start_step or shard")
+        self.device = torch.device(device)
+        self.images = images.to(self.device).contiguous()
+        self.labels = labels.to(self.device, torch.int64).contiguous()
+        self.batch_size = int(batch_size)
+        self.training = bool(training)
+        self.augment = bool(augment)
+        self.pad = int(pad)
+        self.cutout_pad = int(cutout_pad)
+        self.seed = int(seed or 0)
+        self.start_step = int(start_step)
+        self.shard = (rank, world)
+        scale, shift = self._affine(normalize, images.dtype, images.shape[1])
+        self.scale = scale.to(self.device)
+        self.shift = shift.to(self.device)
+
+    @staticmethod
+    def _affine(normalize, dtype, channels: int):
+        """Per-channel fp32 (scale, shift) of ``x * scale + shift``."""
+        unit = 1.0 / 255.0 if dtype == torch.uint8 else 1.0
+        if isinstance(normalize, str):
+            if normalize not in ("unit", "none"):
+                raise ValueError("DeviceImageLoader: normalize must be "
+                                 "'unit', 'none' or (mean, std)")
+            if normalize == "unit" and dtype == torch.uint8:
+                scale, shift = [2.0 / 255.0] * channels, [-1.0] * channels
+            else:
+                scale, shift = [unit] * channels, [0.0] * channels
+        else:
+            mean, std = ([float(v) for v in seq] for seq in normalize)
+            if len(mean) != channels or len(std) != channels:
+                raise ValueError("DeviceImageLoader: mean and std need one "
+                                 "entry per channel")
+            scale = [unit / s for s in std]
+            shift = [-m / s for m, s in zip(mean, std)]
+        return (torch.tensor(scale, dtype=torch.float32),
+                torch.tensor(shift, dtype=torch.float32))
+
+    def __len__(self):
+        if self.training:
+            raise TypeError("a training DeviceImageLoader is endless")
+        return -(-self.images.shape[0] // self.batch_size)
+
+    def __call__(self):
+        return self._train_iter() if self.training else self._eval_iter()
+
+    def _train_iter(self):
+        from adanet_amd.ops import augment as A
+        n, _, h, w = self.images.shape
+        cut = self.cutout_pad if self.augment else 0
+        step = self.start_step
+        while True:
+            params, y = A.draw_params(
+                self.seed, step, self.batch_size, n, h, w, self.pad,
+                self.labels, rank=self.shard[0], world=self.shard[1],
+                augment=self.augment)
+            x = A.augment_apply(self.images, params, self.scale, self.shift,
+                                self.pad, cut)
+            yield x, y
+            step += 1
+
+    def _eval_iter(self):
+        from adanet_amd.ops import augment as A
+        n = self.images.shape[0]
+        for i in range(self.start_step, len(self)):
+            lo = i * self.batch_size
+            hi = min(n, lo + self.batch_size)
+            # index = lo..hi-1, zero crop offset against zero padding, no
+            # flip, cutout off: the image itself, normalised.
+            params = torch.zeros((hi - lo, A.FIELDS), device=self.device,
+                                 dtype=torch.int32)
+            params[:, 0] = torch.arange(lo, hi, device=self.device,
+                                        dtype=torch.int32)
+            x = A.augment_apply(self.images, params, self.scale, self.shift,
+                                0, 0)
+            x.adanet_cache_key = ("image-eval", id(self), i)
+            yield x, self.labels[lo:hi]

@@ -90,6 +90,26 @@ class Provider(object):
 
         return input_fn
 
+    def _raw_data(self, training: bool):
+        """(images, labels) as stored: uint8 where the source is uint8,
+        else the float tensor ``_data`` returns."""
+        return self._data(training)
+
+    def get_device_input_fn(self, device, partition: str = "train",
+                            training: bool = True, normalize="unit"):
+        """Returns a ``data.DeviceImageLoader`` over this provider's data:
+        the dataset is uploaded to ``device`` once (uint8 when the source is
+        uint8) and every batch is drawn, augmented, normalised and cast to
+        bf16 on the device. ``training=False`` visits each example once, in
+        order, unaugmented. The augmentation stream comes from the counter
+        RNG, not from ``get_input_fn``'s host generator."""
+        from adanet_amd.data import DeviceImageLoader
+        X, Y = self._raw_data(training=partition == "train")
+        return DeviceImageLoader(
+            X, Y, self.batch_size, device, training=training,
+            augment=self.augment, cutout_pad=self.cutout_pad,
+            normalize=normalize, seed=self.seed or 0)
+
 
 class FakeImageProvider(Provider):
     """Deterministic synthetic images (reference fake_data.py:26)."""
@@ -109,7 +129,7 @@ class FakeImageProvider(Provider):
         return self._X, self._Y
 
 
-def _load_cifar_binaries(data_dir: str, n_classes: int, training: bool):
+def _load_cifar_binaries_raw(data_dir: str, n_classes: int, training: bool):
     """Reads the standard CIFAR binary distribution (the format in
     cifar-10-binary.tar.gz / cifar-100-binary.tar.gz):
 
@@ -118,8 +138,8 @@ def _load_cifar_binaries(data_dir: str, n_classes: int, training: bool):
       * CIFAR-100: train.bin / test.bin, records of 2 label bytes
         (coarse, fine) + 3072 RGB bytes.
 
-    Returns (x [N,3,32,32] float in [0,1], y [N] long) or None if the
-    files are absent. No torchvision / no network required.
+    Returns (x [N,3,32,32] uint8, y [N] long) or None if the files are
+    absent. No torchvision / no network required.
     """
     import os
 
@@ -148,9 +168,18 @@ def _load_cifar_binaries(data_dir: str, n_classes: int, training: bool):
         raw = raw.reshape(-1, rec)
         ys.append(raw[:, label_off].astype(np.int64))
         xs.append(raw[:, rec - 3072:].reshape(-1, 3, 32, 32))
-    x = torch.from_numpy(np.concatenate(xs)).float() / 255.0
+    x = torch.from_numpy(np.concatenate(xs))
     y = torch.from_numpy(np.concatenate(ys)).long()
     return x, y
+
+
+def _load_cifar_binaries(data_dir: str, n_classes: int, training: bool):
+    """``_load_cifar_binaries_raw`` scaled for the host path: (x [N,3,32,32]
+    float in [0,1], y [N] long), or None if the files are absent."""
+    raw = _load_cifar_binaries_raw(data_dir, n_classes, training)
+    if raw is None:
+        return None
+    return raw[0].float() / 255.0, raw[1]
 
 
 class Cifar10Provider(Provider):
@@ -172,8 +201,11 @@ class Cifar10Provider(Provider):
     def has_real_data(self) -> bool:
         return self._load(True) is not None
 
-    def _load(self, training: bool):
-        key = bool(training)
+    def _load_raw(self, training: bool):
+        """The data as stored, NCHW: (uint8 or float x, long y, whether x
+        always holds bytes to scale by 1/255), or None. Only a uint8 source
+        stays uint8; a float .npz comes back exactly as ``_load`` gives it."""
+        key = ("raw", bool(training))
         if key in self._cache:
             return self._cache[key]
         out = None
@@ -187,15 +219,35 @@ class Cifar10Provider(Provider):
                 xk = "x_train" if training else "x_test"
                 yk = "y_train" if training else "y_test"
                 if xk in z:
-                    x = torch.from_numpy(z[xk]).float()
+                    x = torch.from_numpy(z[xk])
+                    if x.dtype != torch.uint8:
+                        x = x.float()
                     if x.dim() == 4 and x.shape[-1] == 3:  # NHWC -> NCHW
                         x = x.permute(0, 3, 1, 2).contiguous()
-                    if float(x.max()) > 1.5:
+                    if x.dtype != torch.uint8 and float(x.max()) > 1.5:
                         x = x / 255.0
-                    out = (x, torch.from_numpy(z[yk]).long().reshape(-1))
+                    y = torch.from_numpy(z[yk]).long().reshape(-1)
+                    out = (x, y, False)
             if out is None:
-                out = _load_cifar_binaries(self._data_dir, self.n_classes,
-                                           training)
+                raw = _load_cifar_binaries_raw(self._data_dir,
+                                               self.n_classes, training)
+                if raw is not None:
+                    out = (raw[0], raw[1], True)
+        self._cache[key] = out
+        return out
+
+    def _load(self, training: bool):
+        key = bool(training)
+        if key in self._cache:
+            return self._cache[key]
+        out = self._load_raw(training)
+        if out is not None:
+            x, y, is_bytes = out
+            if x.dtype == torch.uint8:
+                x = x.float()
+                if is_bytes or float(x.max()) > 1.5:
+                    x = x / 255.0
+            out = (x, y)
         self._cache[key] = out
         return out
 
@@ -206,6 +258,12 @@ class Cifar10Provider(Provider):
         fake = FakeImageProvider(n_classes=self.n_classes, n_examples=512,
                                  seed=self.seed)
         return fake._data(training)
+
+    def _raw_data(self, training: bool):
+        real = self._load_raw(training)
+        if real is not None:
+            return real[0], real[1]
+        return self._data(training)
 
 
 class Cifar100Provider(Cifar10Provider):

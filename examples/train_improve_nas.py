@@ -24,6 +24,9 @@ def main():
                    choices=["none", "adaptive", "born_again"])
     p.add_argument("--batch-size", type=int, default=64)
     p.add_argument("--model-dir", default="/tmp/adanet_improve_nas")
+    p.add_argument("--device-pipeline", action="store_true",
+                   help="keep the dataset on the training device and build "
+                        "every batch there (data.DeviceImageLoader)")
     args = p.parse_args()
 
     hp = improve_nas.Hparams(
@@ -35,6 +38,9 @@ def main():
     provider = FakeImageProvider(n_classes=10, n_examples=512,
                                  batch_size=args.batch_size, seed=1)
     input_fn = provider.get_input_fn()
+    config = adanet_amd.RunConfig(tf_random_seed=1)
+    if args.device_pipeline:
+        input_fn = provider.get_device_input_fn(config.resolve_device())
 
     estimator = adanet_amd.Estimator(
         head=MultiClassHead(10, label_smoothing=hp.label_smoothing),
@@ -43,7 +49,7 @@ def main():
         force_grow=hp.force_grow,
         max_iterations=args.boosting_iterations,
         model_dir=args.model_dir,
-        config=adanet_amd.RunConfig(tf_random_seed=1),
+        config=config,
     )
     estimator.train(
         input_fn, max_steps=args.boosting_iterations * args.train_steps)

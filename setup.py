@@ -28,6 +28,7 @@ SRC = [
     "adanet_amd/csrc/im2col.hip",
     "adanet_amd/csrc/elementwise.hip",
     "adanet_amd/csrc/combine.hip",
+    "adanet_amd/csrc/augment.hip",
     "adanet_amd/csrc/reduce.hip",
     "adanet_amd/csrc/depthwise.hip",
 ]
