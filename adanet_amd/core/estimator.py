@@ -431,15 +431,36 @@ class Estimator(object):
     def train_and_evaluate(self, train_input_fn, eval_input_fn,
                            max_steps: Optional[int] = None,
                            eval_steps: Optional[int] = None,
-                           hooks=None) -> Dict[str, float]:
+                           hooks=None,
+                           streaming: bool = False) -> Dict[str, float]:
         """tf.estimator.train_and_evaluate analog: train to max_steps, then
-        evaluate the frozen best ensemble."""
+        evaluate the frozen best ensemble (``streaming``: see evaluate)."""
         self.train(train_input_fn, max_steps=max_steps, hooks=hooks)
-        return self.evaluate(eval_input_fn, steps=eval_steps)
+        return self.evaluate(eval_input_fn, steps=eval_steps,
+                             streaming=streaming)
 
     def evaluate(self, input_fn, steps: Optional[int] = None,
-                 checkpoint_path: Optional[str] = None) -> Dict[str, float]:
-        """Evaluates the best ensemble (reference estimator.py:1001-1030)."""
+                 checkpoint_path: Optional[str] = None,
+                 streaming: bool = False,
+                 streaming_options: Optional[dict] = None
+                 ) -> Dict[str, float]:
+        """Evaluates the best ensemble (reference estimator.py:1001-1030).
+
+        By default every head metric and the loss are computed per batch
+        and averaged with equal weight per batch. With ``streaming=True``
+        the head's ``streaming_metrics()`` state accumulates on the device
+        without a host sync per batch and is read once after the loop: the
+        metrics are those of the whole dataset (example-weighted, one AUC
+        histogram) and ``loss`` is the ``average_loss``.
+        ``streaming_options`` are passed to ``streaming_metrics()`` (e.g.
+        ``{"k": 5, "per_class": True}``). A user ``metric_fn`` keeps the
+        per-batch mean either way.
+        """
+        if streaming:
+            return self._evaluate_streaming(input_fn, steps, checkpoint_path,
+                                            streaming_options or {})
+        if streaming_options:
+            raise ValueError("streaming_options need streaming=True")
         ensemble, arch = self._load_frozen_best(checkpoint_path)
         metrics_sum: Dict[str, float] = {}
         count = 0
@@ -467,6 +488,9 @@ class Estimator(object):
             step += 1
         out = {k: v / max(count, 1) for k, v in metrics_sum.items()}
         out["loss"] = loss_sum / max(count, 1)
+        return self._finish_eval_dict(out, arch)
+
+    def _finish_eval_dict(self, out, arch):
         out["global_step"] = self._global_step
         out["architecture/adanet/ensembles"] = (
             arch.serialize(self._iteration_number, self._global_step)
@@ -474,6 +498,35 @@ class Estimator(object):
         for i, idx in enumerate(self._replay_indices):
             out["best_ensemble_index_%d" % i] = idx
         return out
+
+    def _evaluate_streaming(self, input_fn, steps, checkpoint_path, options):
+        """evaluate(streaming=True): per batch only the ensemble forward and
+        the head state's update run; the state is read once at the end."""
+        ensemble, arch = self._load_frozen_best(checkpoint_path)
+        state = self._head.streaming_metrics(device=self._device, **options)
+        user_sum: Dict[str, float] = {}
+        count = 0
+        it = iter(input_fn())
+        while steps is None or count < steps:
+            try:
+                features, labels = next(it)
+            except StopIteration:
+                break
+            features, labels = _to_device(features, labels, self._device)
+            with torch.no_grad():
+                logits = ensemble(features)
+                state.update(logits, labels)
+                if self._metric_fn is not None:
+                    user = self._metric_fn(
+                        predictions=self._head.predictions(logits),
+                        features=features, labels=labels)
+                    for k, v in user.items():
+                        user_sum[k] = user_sum.get(k, 0.0) + float(v)
+            count += 1
+        out = dict(state.result())
+        out.update({k: v / max(count, 1) for k, v in user_sum.items()})
+        out["loss"] = out.get("average_loss", float("nan"))
+        return self._finish_eval_dict(out, arch)
 
     def predict(self, input_fn, checkpoint_path: Optional[str] = None):
         """Yields per-example prediction dicts (reference :1031-1054)."""
@@ -972,7 +1025,8 @@ class Estimator(object):
             local = iteration.evaluate_candidates(
                 iter(self._evaluator.input_fn()), self._evaluator.steps,
                 lambda f, l: _to_device(f, l, self._device),
-                metric_name=self._evaluator.metric_name)
+                metric_name=self._evaluator.metric_name,
+                streaming=getattr(self._evaluator, "streaming", False))
             merged = comm.all_gather_objects({
                 i: v for i, v in enumerate(local)
                 if iteration.ensemble_specs[i].ensemble is not None

@@ -30,6 +30,36 @@ class _MeanAccumulator(object):
         return self.total / self.count if self.count else float("nan")
 
 
+def binary_metrics_from_histogram(hist) -> Dict[str, float]:
+    """auc / precision / recall from a host ``[2, T]`` score histogram
+    (positives in row 0). Shared by AUCAccumulator and the streaming binary
+    head state (head.py), so both read one histogram the same way."""
+    import torch
+    h = hist.long()
+    pos, neg = h[0], h[1]
+    T = int(pos.shape[0])
+    # TP/FP predicting positive at threshold = bucket lower edge
+    # (suffix-inclusive), thresholds 0..T-1 plus the all-negative end.
+    tp = torch.flip(torch.cumsum(torch.flip(pos, [0]), 0), [0])
+    fp = torch.flip(torch.cumsum(torch.flip(neg, [0]), 0), [0])
+    p, n = int(pos.sum()), int(neg.sum())
+    if p == 0 or n == 0:
+        auc = float("nan")
+    else:
+        tpr = tp.double() / p
+        fpr = fp.double() / n
+        # thresholds descend left->right along the ROC; append (0,0)
+        tpr = torch.cat([tpr, torch.zeros(1, dtype=torch.float64)])
+        fpr = torch.cat([fpr, torch.zeros(1, dtype=torch.float64)])
+        auc = float(torch.trapz(tpr.flip(0), fpr.flip(0)))
+    mid = T // 2
+    tp5, fp5 = int(tp[mid]), int(fp[mid])
+    fn5 = p - tp5
+    precision = tp5 / (tp5 + fp5) if (tp5 + fp5) else float("nan")
+    recall = tp5 / (tp5 + fn5) if (tp5 + fn5) else float("nan")
+    return {"auc": auc, "precision": precision, "recall": recall}
+
+
 class AUCAccumulator(object):
     """Streaming thresholded AUC / precision / recall for binary heads.
 
@@ -65,37 +95,11 @@ class AUCAccumulator(object):
             self._hist[0] += pos.to(torch.int32)
             self._hist[1] += neg.to(torch.int32)
 
-    def _counts(self):
-        import torch
-        h = self._hist.cpu().long()
-        pos, neg = h[0], h[1]
-        # TP/FP predicting positive at threshold = bucket lower edge
-        # (suffix-inclusive), thresholds 0..T-1 plus the all-negative end.
-        tp = torch.flip(torch.cumsum(torch.flip(pos, [0]), 0), [0])
-        fp = torch.flip(torch.cumsum(torch.flip(neg, [0]), 0), [0])
-        return tp, fp, int(pos.sum()), int(neg.sum())
-
     def value(self) -> Dict[str, float]:
         if self._hist is None:
             return {"auc": float("nan"), "precision": float("nan"),
                     "recall": float("nan")}
-        tp, fp, p, n = self._counts()
-        if p == 0 or n == 0:
-            auc = float("nan")
-        else:
-            tpr = tp.double() / p
-            fpr = fp.double() / n
-            # thresholds descend left->right along the ROC; append (0,0)
-            import torch
-            tpr = torch.cat([tpr, torch.zeros(1, dtype=torch.float64)])
-            fpr = torch.cat([fpr, torch.zeros(1, dtype=torch.float64)])
-            auc = float(torch.trapz(tpr.flip(0), fpr.flip(0)))
-        mid = self.T // 2
-        tp5, fp5 = int(tp[mid]), int(fp[mid])
-        fn5 = p - tp5
-        precision = tp5 / (tp5 + fp5) if (tp5 + fp5) else float("nan")
-        recall = tp5 / (tp5 + fn5) if (tp5 + fn5) else float("nan")
-        return {"auc": auc, "precision": precision, "recall": recall}
+        return binary_metrics_from_histogram(self._hist.cpu())
 
 
 class _EvalMetricsStore(object):

@@ -25,17 +25,26 @@ class Evaluator(object):
     """Scores every candidate ensemble on `steps` shared batches of
     `input_fn` and selects argmin/argmax of `metric_name` (default
     adanet_loss; any head metric works — e.g. accuracy with MAXIMIZE).
-    Reference adanet/core/evaluator.py:31-140."""
+    Reference adanet/core/evaluator.py:31-140.
+
+    A head metric is by default the mean of its per-batch values. With
+    `streaming=True` every candidate gets one `head.streaming_metrics()`
+    state, updated per batch without a host sync and read once at the end:
+    the candidates are then compared on the whole-dataset metric (e.g. the
+    dataset AUC, not the mean of batch AUCs). It has no effect on
+    `adanet_loss`."""
 
     def __init__(self, input_fn, steps: Optional[int] = None,
                  metric_name: str = "adanet_loss",
-                 objective: str = Objective.MINIMIZE):
+                 objective: str = Objective.MINIMIZE,
+                 streaming: bool = False):
         if objective not in (Objective.MINIMIZE, Objective.MAXIMIZE):
             raise ValueError("objective must be 'minimize' or 'maximize'")
         self._input_fn = input_fn
         self._steps = steps
         self._metric_name = metric_name
         self._objective = objective
+        self._streaming = bool(streaming)
 
     @property
     def input_fn(self):
@@ -52,6 +61,10 @@ class Evaluator(object):
     @property
     def objective(self):
         return self._objective
+
+    @property
+    def streaming(self):
+        return self._streaming
 
     def evaluate(self, metric_fns: Sequence[Callable],
                  input_iter=None) -> List[float]:

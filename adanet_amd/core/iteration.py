@@ -887,13 +887,23 @@ class _Iteration(object):
 
     def evaluate_candidates(self, input_iter, steps: Optional[int],
                             to_device: Callable,
-                            metric_name: str = "adanet_loss") -> List[float]:
+                            metric_name: str = "adanet_loss",
+                            streaming: bool = False) -> List[float]:
         """Mean eval metric per candidate over shared eval batches
         (reference evaluator.py:97-140: same batches for all candidates).
         Default metric is the fused adanet_loss; any head metric (e.g.
         "accuracy" with a MAXIMIZE objective) may drive selection.
+        With `streaming` a head metric is that of the whole eval set: one
+        head.streaming_metrics() state per candidate, updated per batch
+        without a sync and read once per candidate at the end.
         Round-robin: each rank evaluates the candidates it owns; results
         are merged by adanet_losses()-style all-gather in the caller."""
+        streaming = streaming and metric_name != "adanet_loss"
+        states = [
+            self.head.streaming_metrics(device=self.device)
+            if streaming and spec.ensemble is not None else None
+            for spec in self.ensemble_specs
+        ]
         # Accumulate per-candidate losses as DEVICE tensors: one host sync
         # per candidate at the end instead of candidates x eval-batches
         # blocking .item() round-trips mid-phase.
@@ -917,6 +927,14 @@ class _Iteration(object):
                 for i, spec in enumerate(self.ensemble_specs):
                     if spec.ensemble is None:
                         continue
+                    if streaming:
+                        sub_logits, sub_last = self._gather_member_outputs(
+                            spec, frozen_out)
+                        if sub_logits is not None:
+                            states[i].update(
+                                spec.ensemble.logits_from(sub_logits,
+                                                          sub_last), labels)
+                        continue
                     if metric_name == "adanet_loss":
                         loss = self._ensemble_adanet_loss(
                             spec, frozen_out, labels, train=False)
@@ -934,6 +952,14 @@ class _Iteration(object):
         for i, spec in enumerate(self.ensemble_specs):
             if spec.ensemble is None:
                 out.append(float("nan"))
+            elif streaming:
+                metrics = states[i].result()
+                if metric_name not in metrics:
+                    raise ValueError(
+                        "Evaluator metric_name %r not produced by the head "
+                        "(available: %s)" % (metric_name, sorted(metrics)))
+                spec.eval_loss = float(metrics[metric_name])
+                out.append(spec.eval_loss)
             else:
                 spec.eval_loss = float(sums[i]) / count
                 out.append(spec.eval_loss)

@@ -102,6 +102,14 @@ void augment_apply(const at::Tensor& data, const at::Tensor& params,
 void colsum_bf16(const at::Tensor& x, at::Tensor& out, int64_t accum);
 void binary_histogram(const at::Tensor& scores, const at::Tensor& labels,
                       at::Tensor& hist);
+void metrics_multiclass_update(at::Tensor& state, const at::Tensor& logits,
+                               const at::Tensor& labels, int64_t k,
+                               double eps, bool per_class);
+void metrics_binary_update(at::Tensor& state, const at::Tensor& logits,
+                           const at::Tensor& labels, int64_t T);
+void metrics_regression_update(at::Tensor& state, const at::Tensor& logits,
+                               const at::Tensor& labels);
+int64_t metrics_max_blocks();
 void depthwise_fwd(const at::Tensor& x, const at::Tensor& w, at::Tensor& y,
                    int64_t stride, int64_t pad);
 void depthwise_bwd_dx(const at::Tensor& dy, const at::Tensor& w,
@@ -192,6 +200,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("accum") = 0);
   m.def("argmax_correct", &argmax_correct);
   m.def("binary_histogram", &binary_histogram);
+  m.def("metrics_multiclass_update", &metrics_multiclass_update,
+        "streaming loss / top-1 / top-k / per-class counts into an fp64 state",
+        py::arg("state"), py::arg("logits"), py::arg("labels"), py::arg("k"),
+        py::arg("eps"), py::arg("per_class"));
+  m.def("metrics_binary_update", &metrics_binary_update,
+        "streaming sigmoid loss / accuracy / [2,T] score histogram",
+        py::arg("state"), py::arg("logits"), py::arg("labels"), py::arg("T"));
+  m.def("metrics_regression_update", &metrics_regression_update,
+        "streaming squared / absolute error sums", py::arg("state"),
+        py::arg("logits"), py::arg("labels"));
+  m.def("metrics_max_blocks", &metrics_max_blocks,
+        "grid cap of the streaming-metric update kernels");
   m.def("im2col_bf16", &im2col_bf16);
   m.def("col2im_bf16", &col2im_bf16);
   m.def("pool3_fwd", &pool3_fwd);

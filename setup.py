@@ -30,6 +30,7 @@ SRC = [
     "adanet_amd/csrc/combine.hip",
     "adanet_amd/csrc/augment.hip",
     "adanet_amd/csrc/reduce.hip",
+    "adanet_amd/csrc/eval_metrics.hip",
     "adanet_amd/csrc/depthwise.hip",
 ]
 
