@@ -1,5 +1,8 @@
-"""Refcheck + A/B the LDS-staged depthwise kernels against torch fp32 and
-the previous register-tap kernels (toggle ADANET_DW_OLD=1).
+"""Refcheck the depthwise kernels against torch fp32 and time them.
+
+The A/B against the previous register-tap kernels is historical
+(profiles/dw_new3.json vs dw_old2.json); the switch that selected them is
+gone, and those kernels now serve only images too large for LDS.
 
 The old kernels re-read each input pixel KS^2 times through L1 — fwd<5>
 measured 141 us at a shape whose once-through traffic is ~9 us

@@ -36,16 +36,19 @@ def test_relu_bwd_colsum_bitrepeat(shape):
 def test_depthwise_dw_bitrepeat():
     ext = _ext()
     torch.manual_seed(4)
-    x = (torch.randn(64, 32, 32, 32, device="cuda") / 4).to(torch.bfloat16)
-    dy = (torch.randn(64, 32, 32, 32, device="cuda") / 4).to(torch.bfloat16)
-    ref = None
-    for _ in range(5):
-        dw = torch.empty(32, 25, device="cuda")
-        ext.depthwise_bwd_dw(x, dy, dw, 1, 2)
-        if ref is None:
-            ref = dw.clone()
-        else:
-            assert torch.equal(ref, dw)
+    # Second case: 5 chunks of one image each, while an LDS group holds
+    # G = 5 images, so every chunk ends on a ragged group (ni = 1 < G).
+    for B, C, H, KS in [(64, 32, 32, 5), (5, 7, 16, 3)]:
+        x = (torch.randn(B, C, H, H, device="cuda") / 4).to(torch.bfloat16)
+        dy = (torch.randn(B, C, H, H, device="cuda") / 4).to(torch.bfloat16)
+        ref = None
+        for _ in range(5):
+            dw = torch.empty(C, KS * KS, device="cuda")
+            ext.depthwise_bwd_dw(x, dy, dw, 1, KS // 2)
+            if ref is None:
+                ref = dw.clone()
+            else:
+                assert torch.equal(ref, dw)
 
 
 def test_splitk_bitrepeat_and_no_empty_slots():

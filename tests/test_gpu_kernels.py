@@ -596,12 +596,40 @@ def test_multi_copy_bf16():
         assert torch.equal(s, d)
 
 
-@pytest.mark.parametrize("C,KS,stride", [(24, 3, 1), (32, 5, 2), (7, 3, 2)])
-def test_depthwise_conv_fwd_bwd_vs_fp32(C, KS, stride):
+@pytest.mark.parametrize("B,C,H,W,KS,stride,pad", [
+    # 289 px is no multiple of 8: scalar LDS staging everywhere. These
+    # three keep the ids they had as (C, KS, stride).
+    pytest.param(3, 24, 17, 17, 3, 1, 1, id="24-3-1"),
+    pytest.param(3, 32, 17, 17, 5, 2, 2, id="32-5-2"),
+    pytest.param(3, 7, 17, 17, 3, 2, 1, id="7-3-2"),
+    # LDS fwd/dX image-outer, vectorised staging, ragged last group
+    # (21 images, P = 16); LDS dW with 3 chunks.
+    (3, 7, 16, 16, 3, 1, 1),
+    # LDS fwd flat branch (8x8 outputs); LDS dX<5,2> with vector staging.
+    (3, 7, 16, 16, 5, 2, 2),
+    # KS = 7 on a non-square image (catches H/W swaps); LDS dX<7,1>, <7,2>.
+    (2, 5, 16, 24, 7, 1, 3), (2, 5, 16, 24, 7, 2, 3),
+    (2, 4, 16, 16, 3, 1, 0),  # pad = 0
+    (2, 4, 13, 13, 3, 3, 1),  # stride 3: runtime dX kernel
+    # KS = 9: runtime fwd and dX, tap-per-block dW.
+    (2, 4, 12, 12, 9, 1, 4),
+    # 9216 px > 8192: fwd_tmpl<3>, dx_tmpl<3,1>, dw_fused<3> (64 chunks).
+    (1, 3, 96, 96, 3, 1, 1),
+    # fwd_tmpl<5>; 48x48 dy fits, so LDS dX with P = 1; dw_fused<5>.
+    (1, 3, 96, 96, 5, 2, 2),
+    # runtime fwd (there is no fwd_tmpl<7>), dx_tmpl<7,1>, dw_fused<7>.
+    (1, 2, 96, 96, 7, 1, 3),
+    # 92x92 outputs > 8192 px: dx_tmpl<3,2> and dx_tmpl<7,2>.
+    (1, 2, 184, 184, 3, 2, 1), (1, 2, 184, 184, 7, 2, 3),
+])
+def test_depthwise_conv_fwd_bwd_vs_fp32(B, C, H, W, KS, stride, pad):
+    """Every dispatch tier of csrc/depthwise.hip against torch's fp32 grouped
+    convolution. The one route left uncovered is B*C > 65535 (the grid-y
+    limit, which sends templated tap sizes to the runtime-KS kernels): with
+    images too large for the LDS tiers it needs over half a billion
+    elements."""
     from adanet_amd.ops.conv import _DepthwiseFn
     torch.manual_seed(9)
-    B, H, W = 3, 17, 17
-    pad = KS // 2
     x = torch.randn(B, C, H, W, device=DEV).to(
         torch.bfloat16).requires_grad_(True)
     w = torch.randn(C, 1, KS, KS, device=DEV).mul(0.2).to(
@@ -618,6 +646,20 @@ def test_depthwise_conv_fwd_bwd_vs_fp32(C, KS, stride):
     for got, want in [(x.grad.float(), xf.grad), (w.grad.float(), wf.grad)]:
         rel = (got - want).abs().mean() / (want.abs().mean() + 1e-6)
         assert rel < 0.03, rel
+
+
+def test_depthwise_rejects_bad_arguments():
+    ext = _ext()
+    bf = dict(device=DEV, dtype=torch.bfloat16)
+    w = torch.zeros(4, 1, 3, 3, **bf)
+    dy = torch.zeros(2, 4, 8, 8, **bf)
+    x_strided = torch.zeros(2, 4, 8, 16, **bf)[..., ::2]
+    assert x_strided.shape == dy.shape and not x_strided.is_contiguous()
+    with pytest.raises(RuntimeError):
+        ext.depthwise_bwd_dw(x_strided, dy, torch.empty(36, device=DEV), 1, 1)
+    with pytest.raises(RuntimeError):  # 3x3, stride 1, pad 1 keeps 8x8
+        ext.depthwise_bwd_dx(torch.zeros(2, 4, 7, 7, **bf), w,
+                             torch.empty(2, 4, 8, 8, **bf), 1, 1)
 
 
 def test_conv_nxn_unfold_gemm_vs_fp32():
