@@ -33,11 +33,6 @@ void softmax_xent_bwd(const at::Tensor& probs, const at::Tensor& labels,
                       const c10::optional<at::Tensor>& grad_rows,
                       at::Tensor& dlogits, double eps,
                       const c10::optional<at::Tensor>& grad_scalar);
-void mixer_fwd(const at::Tensor& stack, const at::Tensor& weights,
-               const c10::optional<at::Tensor>& bias, at::Tensor& out,
-               int64_t vector_mode);
-void mixer_bwd_dw(const at::Tensor& stack, const at::Tensor& dY,
-                  at::Tensor& dw, int64_t vector_mode);
 void mixer_bwd_dlogits(const at::Tensor& dY, const at::Tensor& weights,
                        at::Tensor& dL, int64_t j, int64_t vector_mode);
 void mixer_fwd_direct(const std::vector<at::Tensor>& members,
@@ -159,8 +154,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_bf16", &transpose_bf16, "bf16 2-D transpose");
   m.def("softmax_xent_fwd", &softmax_xent_fwd);
   m.def("softmax_xent_bwd", &softmax_xent_bwd);
-  m.def("mixer_fwd", &mixer_fwd);
-  m.def("mixer_bwd_dw", &mixer_bwd_dw);
   m.def("mixer_bwd_dlogits", &mixer_bwd_dlogits);
   m.def("mixer_fwd_direct", &mixer_fwd_direct);
   m.def("mixer_bwd_dw_direct", &mixer_bwd_dw_direct);

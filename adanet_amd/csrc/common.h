@@ -52,6 +52,42 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
   return v;
 }
 
+// The two halves of every deterministic two-stage reduction (ARCHITECTURE.md,
+// "Determinism as a design property"): a block sums into a slot it owns,
+// then one wave per output sums the slots. Both orders are fixed.
+
+// Sum each acc[t] over the 256-thread block; thread 0 hands the total to
+// emit(t, total). The barrier after the emit frees the LDS scratch for the
+// next t and for whatever the caller does next.
+template <int N, typename Emit>
+__device__ __forceinline__ void block_reduce_sum(const float (&acc)[N],
+                                                 Emit emit) {
+  __shared__ float partial[4];
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    const float v = wave_reduce_sum(acc[t]);
+    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      emit(t, partial[0] + partial[1] + partial[2] + partial[3]);
+    __syncthreads();
+  }
+}
+
+// One wave's sum of the n slots base[r * stride]: lane l takes
+// r = l, l + 64, ..., then the xor-shuffle tree. Every lane gets the total.
+__device__ __forceinline__ float wave_slot_sum(const float* __restrict__ base,
+                                               int64_t stride, int n) {
+  float s = 0.f;
+  for (int r = threadIdx.x & 63; r < n; r += 64) s += base[r * stride];
+  return wave_reduce_sum(s);
+}
+
+// out[c] (+)= sum_chunk wsp[chunk][c] on `stream` (colsum_reduce_kernel;
+// defined in reduce.hip so the kernel has one code object).
+void launch_colsum_reduce(const float* wsp, float* out, int C, int nchunks,
+                          int accum, hipStream_t stream);
+
 // Stateless counter-based RNG (pcg-like hash) for dropout: reproducible from
 // (seed, index) so backward can recompute the mask without storing it.
 __device__ __forceinline__ uint32_t hash_rng(uint64_t seed, uint64_t idx) {

@@ -102,23 +102,6 @@ __device__ __forceinline__ void stage_span(bf16_t* dst, const bf16_t* src,
   }
 }
 
-// Sum each acc[t] over the 256-thread block; thread 0 hands the total to
-// emit(t, total).
-template <int N, typename Emit>
-__device__ __forceinline__ void block_reduce_taps(const float (&acc)[N],
-                                                  Emit emit) {
-  __shared__ float partial[4];
-#pragma unroll
-  for (int t = 0; t < N; ++t) {
-    const float v = wave_reduce_sum(acc[t]);
-    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      emit(t, partial[0] + partial[1] + partial[2] + partial[3]);
-    __syncthreads();
-  }
-}
-
 // ---------------------------------------------------------------- forward
 // Runtime-KS kernel: any tap size, flat grid-stride loop over all outputs.
 __global__ __launch_bounds__(256) void depthwise_fwd_kernel(
@@ -294,10 +277,10 @@ __global__ __launch_bounds__(256) void depthwise_bwd_dx_lds_kernel(
 // into a workspace slot; depthwise_dw_reduce_kernel sums chunks in fixed
 // order (deterministic — replaces the per-tap atomicAdd, whose fp32
 // ordering varied run to run).
-// This kernel keeps its hand-written staging, tap loop and reduction: built
-// on shared helpers it kept its registers, occupancy and instruction mix
-// but measured 4-9% slower, twice (256x32x32x32 5x5: 88.5 us against 81.0;
-// BENCHMARKS.md).
+// This kernel keeps its hand-written staging and tap loop: built on the
+// shared staging and tap helpers it kept its registers, occupancy and
+// instruction mix but measured 4-9% slower, twice (256x32x32x32 5x5: 88.5 us
+// against 81.0; BENCHMARKS.md). Only its final block sum is the shared one.
 template <int KS>
 __global__ __launch_bounds__(256) void depthwise_bwd_dw_lds_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
@@ -360,18 +343,8 @@ __global__ __launch_bounds__(256) void depthwise_bwd_dw_lds_kernel(
     }
     __syncthreads();
   }
-  __shared__ float partial[4];
-#pragma unroll
-  for (int t = 0; t < KS * KS; ++t) {
-    float v = wave_reduce_sum(acc[t]);
-    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      wsp[((int64_t)blockIdx.y * C + c) * (KS * KS) + t] =
-          partial[0] + partial[1] + partial[2] + partial[3];
-    }
-    __syncthreads();
-  }
+  float* slot = wsp + ((int64_t)blockIdx.y * C + c) * (KS * KS);
+  block_reduce_sum(acc, [&](int t, float v) { slot[t] = v; });
 }
 
 // dw[c*KSQ+t] = sum over chunks of wsp[(chunk*C + c)*KSQ + t], fixed order.
@@ -422,7 +395,7 @@ __global__ __launch_bounds__(256) void depthwise_bwd_dw_fused_kernel(
       }
     }
   }
-  block_reduce_taps(
+  block_reduce_sum(
       acc, [&](int t, float v) { atomicAdd(&dw[c * KS * KS + t], v); });
 }
 
@@ -446,7 +419,7 @@ __global__ __launch_bounds__(256) void depthwise_bwd_dw_kernel(
     acc[0] += bf2f(dy[((int64_t)b * C + c) * OH * OW + oh * OW + ow]) *
               bf2f(x[((int64_t)b * C + c) * H * W + ih * W + iw]);
   }
-  block_reduce_taps(
+  block_reduce_sum(
       acc, [&](int, float v) { dw[c * KS * KS + kh * KS + kw] = v; });
 }
 

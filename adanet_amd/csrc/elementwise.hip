@@ -61,9 +61,10 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(
 // Layout mirrors colsum: thread-per-column (coalesced), row-chunk grid.y
 // fills the chip (direct-to-arena accum semantics — db never pre-zeroed).
 // Deterministic: each (stripe, chunk) block writes its partial into its
-// OWN workspace slot; a fixed-order reducer finishes (fp32 atomics have
-// run-dependent ordering -> last-ulp bias-grad wobble that flips near-tie
-// candidate selections across otherwise-identical runs).
+// OWN workspace slot; colsum_reduce_kernel (reduce.hip) adds them onto db
+// in fixed order (fp32 atomics have run-dependent ordering -> last-ulp
+// bias-grad wobble that flips near-tie candidate selections across
+// otherwise-identical runs).
 __global__ __launch_bounds__(256) void relu_bwd_colsum_kernel(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
     bf16_t* __restrict__ dz, float* __restrict__ wsp, int B, int C,
@@ -80,22 +81,6 @@ __global__ __launch_bounds__(256) void relu_bwd_colsum_kernel(
     acc += g;
   }
   wsp[(int64_t)blockIdx.y * C + c] = acc;
-}
-
-// db[c] += sum_chunk wsp[chunk][c], chunks reduced lane-parallel within
-// one wave per column then wave-shuffled in FIXED TREE ORDER (still
-// deterministic). Thread-per-column serialized nchunks loads on a
-// near-empty chip (was 11% of the DNN step, bench_kernel_stats_r02c).
-__global__ __launch_bounds__(256) void colsum_chunk_reduce_kernel(
-    const float* __restrict__ wsp, float* __restrict__ db, int C,
-    int nchunks) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (c >= C) return;
-  float s = 0.f;
-  for (int r = lane; r < nchunks; r += 64) s += wsp[(int64_t)r * C + c];
-  s = wave_reduce_sum(s);
-  if (lane == 0) db[c] += s;
 }
 
 // Batched device-to-device copy: up to 8 (src,dst) pairs per launch
@@ -220,9 +205,7 @@ void relu_bwd_colsum(const at::Tensor& dy, const at::Tensor& y,
                      (const bf16_t*)y.data_ptr(), (bf16_t*)dz.data_ptr(),
                      wsp.data_ptr<float>(), B, C, rows_per_block,
                      (float)scale);
-  hipLaunchKernelGGL(colsum_chunk_reduce_kernel,
-                     dim3((unsigned)((C + 3) / 4)), dim3(256), 0,
-                     stream.stream(), wsp.data_ptr<float>(),
-                     db.data_ptr<float>(), C, row_chunks);
+  launch_colsum_reduce(wsp.data_ptr<float>(), db.data_ptr<float>(), C,
+                       row_chunks, /*accum=*/1, stream.stream());
   HIP_CHECK_KERNEL();
 }

@@ -6,55 +6,11 @@
 // where w_j is a scalar (MixtureWeightType.SCALAR) or per-class vector
 // (VECTOR). The production path reads the J member buffers IN PLACE via
 // kernel-arg pointer structs (mixer_*_direct below — no per-step stack
-// copy; hipGraph capture bakes the stable static-buffer addresses). The
-// older stacked-[J,B,C] entry points are kept for the probe/tests.
+// copy; hipGraph capture bakes the stable static-buffer addresses).
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
-
-__global__ __launch_bounds__(256) void mixer_fwd_kernel(
-    const bf16_t* __restrict__ stack, const float* __restrict__ w,
-    const float* __restrict__ bias, bf16_t* __restrict__ out, int J, int B,
-    int C, int64_t stride_j, bf16_t* __restrict__ outdst_unused,
-    int ldo, int vector_mode) {
-  const int64_t total = (int64_t)B * C;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
-       p += (int64_t)gridDim.x * blockDim.x) {
-    const int b = (int)(p / C), c = (int)(p % C);
-    float acc = bias ? bias[c] : 0.f;
-    const int64_t off = (int64_t)b * C + c;
-    for (int j = 0; j < J; ++j) {
-      const float wj = vector_mode ? w[j * C + c] : w[j];
-      acc += wj * bf2f(stack[j * stride_j + off]);
-    }
-    out[(int64_t)b * ldo + c] = f2bf(acc);
-  }
-}
-
-// dw for SCALAR weights: dw[j] = sum_{b,c} dY[b,c] * L[j,b,c].
-__global__ __launch_bounds__(256) void mixer_bwd_dw_scalar_kernel(
-    const bf16_t* __restrict__ stack, const bf16_t* __restrict__ dY,
-    float* __restrict__ wsp, int J, int B, int C, int64_t stride_j,
-    int ldy) {
-  const int j = blockIdx.y;
-  const bf16_t* L = stack + j * stride_j;
-  const int64_t total = (int64_t)B * C;
-  float acc = 0.f;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
-       p += (int64_t)gridDim.x * blockDim.x) {
-    const int b = (int)(p / C), c = (int)(p % C);
-    acc += bf2f(dY[(int64_t)b * ldy + c]) * bf2f(L[(int64_t)b * C + c]);
-  }
-  acc = wave_reduce_sum(acc);
-  __shared__ float partial[4];
-  if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    wsp[(int64_t)j * gridDim.x + blockIdx.x] =
-        partial[0] + partial[1] + partial[2] + partial[3];
-  }
-}
 
 // dw[j] += sum_b wsp[j][b] in fixed block order (dw holds the running
 // arena gradient — accumulate, never overwrite).
@@ -66,21 +22,6 @@ __global__ void mixer_dw_reduce_kernel(const float* __restrict__ wsp,
   float s = 0.f;
   for (int b = 0; b < nblocks; ++b) s += wsp[(int64_t)j * nblocks + b];
   dw[j] += s;
-}
-
-// dw for VECTOR weights: dw[j][c] = sum_b dY[b,c] * L[j,b,c].
-__global__ __launch_bounds__(256) void mixer_bwd_dw_vector_kernel(
-    const bf16_t* __restrict__ stack, const bf16_t* __restrict__ dY,
-    float* __restrict__ dw, int J, int B, int C, int64_t stride_j, int ldy) {
-  const int j = blockIdx.y;
-  const bf16_t* L = stack + j * stride_j;
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C;
-       c += gridDim.x * blockDim.x) {
-    float acc = 0.f;
-    for (int b = 0; b < B; ++b)
-      acc += bf2f(dY[(int64_t)b * ldy + c]) * bf2f(L[(int64_t)b * C + c]);
-    dw[j * C + c] = acc;
-  }
 }
 
 // dL_j = w_j * dY (only trainable members need it).
@@ -126,6 +67,7 @@ __global__ __launch_bounds__(256) void mixer_fwd_ptrs_kernel(
   }
 }
 
+// dw for SCALAR weights: dw[j] = sum_{b,c} dY[b,c] * L[j,b,c].
 // Deterministic: each block writes its partial into wsp[j][blockIdx.x];
 // mixer_dw_reduce_kernel sums in fixed block order (fp32 atomics had
 // run-dependent ordering -> last-ulp dw wobble across identical runs).
@@ -136,22 +78,18 @@ __global__ __launch_bounds__(256) void mixer_bwd_dw_scalar_ptrs_kernel(
   const bf16_t* L = Ls.p[j];
   const int ldl = Ls.ld[j];
   const int64_t total = (int64_t)B * C;
-  float acc = 0.f;
+  float acc[1] = {0.f};
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
        p += (int64_t)gridDim.x * blockDim.x) {
     const int b = (int)(p / C), c = (int)(p % C);
-    acc += bf2f(dY[(int64_t)b * ldy + c]) * bf2f(L[(int64_t)b * ldl + c]);
+    acc[0] += bf2f(dY[(int64_t)b * ldy + c]) * bf2f(L[(int64_t)b * ldl + c]);
   }
-  acc = wave_reduce_sum(acc);
-  __shared__ float partial[4];
-  if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    wsp[(int64_t)j * gridDim.x + blockIdx.x] =
-        partial[0] + partial[1] + partial[2] + partial[3];
-  }
+  block_reduce_sum(acc, [&](int, float v) {
+    wsp[(int64_t)j * gridDim.x + blockIdx.x] = v;
+  });
 }
 
+// dw for VECTOR weights: dw[j][c] = sum_b dY[b,c] * L[j,b,c].
 __global__ __launch_bounds__(256) void mixer_bwd_dw_vector_ptrs_kernel(
     MixerPtrs Ls, const bf16_t* __restrict__ dY, float* __restrict__ dw,
     int B, int C, int ldy) {
@@ -248,54 +186,6 @@ void mixer_bwd_dw_direct(const std::vector<at::Tensor>& members,
     }
     HIP_CHECK_KERNEL();
   }
-}
-
-void mixer_fwd(const at::Tensor& stack, const at::Tensor& weights,
-               const c10::optional<at::Tensor>& bias, at::Tensor& out,
-               int64_t vector_mode) {
-  TORCH_CHECK(stack.dim() == 3 && stack.is_contiguous(),
-              "mixer: stacked [J,B,C] contiguous bf16 required");
-  const int J = (int)stack.size(0), B = (int)stack.size(1),
-            C = (int)stack.size(2);
-  if (J == 0 || (int64_t)B * C == 0) return;
-  auto stream = at::cuda::getCurrentCUDAStream();
-  const float* bias_ptr =
-      (bias.has_value() && bias->defined()) ? bias->data_ptr<float>() : nullptr;
-  hipLaunchKernelGGL(mixer_fwd_kernel, dim3(grid_for((int64_t)B * C)),
-                     dim3(256), 0, stream.stream(),
-                     (const bf16_t*)stack.data_ptr(),
-                     weights.data_ptr<float>(), bias_ptr,
-                     (bf16_t*)out.data_ptr(), J, B, C,
-                     (int64_t)stack.stride(0), nullptr, (int)out.stride(0),
-                     (int)vector_mode);
-  HIP_CHECK_KERNEL();
-}
-
-void mixer_bwd_dw(const at::Tensor& stack, const at::Tensor& dY,
-                  at::Tensor& dw, int64_t vector_mode) {
-  const int J = (int)stack.size(0), B = (int)stack.size(1),
-            C = (int)stack.size(2);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  if (vector_mode) {
-    dim3 grid((unsigned)((C + 255) / 256), (unsigned)J);
-    hipLaunchKernelGGL(mixer_bwd_dw_vector_kernel, grid, dim3(256), 0,
-                       stream.stream(), (const bf16_t*)stack.data_ptr(),
-                       (const bf16_t*)dY.data_ptr(), dw.data_ptr<float>(), J,
-                       B, C, (int64_t)stack.stride(0), (int)dY.stride(0));
-  } else {
-    dim3 grid(
-        (unsigned)std::min<int64_t>(((int64_t)B * C + 2047) / 2048, 256),
-        (unsigned)J);
-    auto wsp = at::empty({J, (int)grid.x}, dw.options());
-    hipLaunchKernelGGL(mixer_bwd_dw_scalar_kernel, grid, dim3(256), 0,
-                       stream.stream(), (const bf16_t*)stack.data_ptr(),
-                       (const bf16_t*)dY.data_ptr(), wsp.data_ptr<float>(),
-                       J, B, C, (int64_t)stack.stride(0), (int)dY.stride(0));
-    hipLaunchKernelGGL(mixer_dw_reduce_kernel, dim3(1), dim3(64), 0,
-                       stream.stream(), wsp.data_ptr<float>(),
-                       dw.data_ptr<float>(), J, (int)grid.x);
-  }
-  HIP_CHECK_KERNEL();
 }
 
 void mixer_bwd_dlogits(const at::Tensor& dY, const at::Tensor& weights,

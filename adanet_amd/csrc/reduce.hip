@@ -34,20 +34,24 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(
 // out[c] (+)= sum_chunk wsp[chunk][c]: one wave per column, lanes over
 // chunks, fixed-tree wave reduce — deterministic and chip-filling (the
 // thread-per-column version serialized nchunks loads; at C=10 it ran 10
-// threads x 256 loads and was 10% of the DNN step).
+// threads x 256 loads and was 10% of the DNN step; under relu_bwd_colsum
+// it was 11% of the DNN step, bench_kernel_stats_r02c).
 __global__ __launch_bounds__(256) void colsum_reduce_kernel(
     const float* __restrict__ wsp, float* __restrict__ out, int C,
     int nchunks, int accum) {
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
   if (c >= C) return;
-  float s = 0.f;
-  for (int r = lane; r < nchunks; r += 64) s += wsp[(int64_t)r * C + c];
-  s = wave_reduce_sum(s);
-  if (lane == 0) {
+  const float s = wave_slot_sum(wsp + c, C, nchunks);
+  if ((threadIdx.x & 63) == 0) {
     if (accum) out[c] += s;
     else out[c] = s;
   }
+}
+
+void launch_colsum_reduce(const float* wsp, float* out, int C, int nchunks,
+                          int accum, hipStream_t stream) {
+  hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((C + 3) / 4)),
+                     dim3(256), 0, stream, wsp, out, C, nchunks, accum);
 }
 
 // argmax over the class dim + count of matches with labels (accuracy numer).
@@ -128,26 +132,21 @@ void colsum_bf16(const at::Tensor& x, at::Tensor& out, int64_t accum) {
   // Fill the chip: aim for ~1024 blocks, at least 8 rows per chunk.
   int row_chunks = std::max(1, std::min(1024 / stripes, (B + 7) / 8));
   const int rows_per_block = (B + row_chunks - 1) / row_chunks;
+  // A single chunk writes `out` itself: no workspace, no second launch.
+  float* wsp = nullptr;
+  at::Tensor wsp_t;
   if (row_chunks > 1) {
-    auto wsp = at::empty({row_chunks, C}, out.options());
-    hipLaunchKernelGGL(colsum_bf16_kernel,
-                       dim3((unsigned)stripes, (unsigned)row_chunks),
-                       dim3(256), 0, stream.stream(),
-                       (const bf16_t*)x.data_ptr(), out.data_ptr<float>(), B,
-                       C, (int)x.stride(0), rows_per_block, (int)accum,
-                       wsp.data_ptr<float>());
-    hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((C + 3) / 4)),
-                       dim3(256), 0, stream.stream(),
-                       wsp.data_ptr<float>(), out.data_ptr<float>(), C,
-                       row_chunks, (int)accum);
-    HIP_CHECK_KERNEL();
-    return;
+    wsp_t = at::empty({row_chunks, C}, out.options());
+    wsp = wsp_t.data_ptr<float>();
   }
   hipLaunchKernelGGL(colsum_bf16_kernel,
                      dim3((unsigned)stripes, (unsigned)row_chunks), dim3(256),
                      0, stream.stream(), (const bf16_t*)x.data_ptr(),
                      out.data_ptr<float>(), B, C, (int)x.stride(0),
-                     rows_per_block, (int)accum, (float*)nullptr);
+                     rows_per_block, (int)accum, wsp);
+  if (wsp)
+    launch_colsum_reduce(wsp, out.data_ptr<float>(), C, row_chunks,
+                         (int)accum, stream.stream());
   HIP_CHECK_KERNEL();
 }
 

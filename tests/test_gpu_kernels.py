@@ -151,11 +151,12 @@ def test_softmax_xent_strided_view():
 
 
 # ------------------------------------------------------------- mixer K5
+@pytest.mark.parametrize("J", [5, 11])  # 11: two launches, 8 + 3 members
 @pytest.mark.parametrize("vector_mode", [False, True])
-def test_mixer_fwd_bwd(vector_mode):
+def test_mixer_fwd_bwd(vector_mode, J):
     from adanet_amd.ops.mixer import weighted_sum_logits
     torch.manual_seed(0)
-    J, B, C = 5, 128, 10
+    B, C = 128, 10
     logits = [torch.randn(B, C, device=DEV).to(torch.bfloat16)
               for _ in range(J)]
     logits[-1].requires_grad_(True)
@@ -697,12 +698,16 @@ def test_conv_nxn_unfold_gemm_vs_fp32():
 
 
 # ------------------------------------------------------------ batchnorm K8
-def test_batchnorm_train_fwd_bwd_vs_fp32():
+@pytest.mark.parametrize("N,C,H,W", [
+    (8, 32, 16, 16),   # 8 image chunks per channel + finalize
+    (1, 16, 8, 8),     # one image: a single chunk finishes in place
+    (2, 1100, 4, 4),   # C > 1024: a single chunk as well
+])
+def test_batchnorm_train_fwd_bwd_vs_fp32(N, C, H, W):
     """Native BN (csrc/batchnorm.hip) vs torch fp32 BatchNorm2d: forward,
     running stats, and dx/dgamma/dbeta in train mode."""
     from adanet_amd.ops.batchnorm import HipBatchNorm2d
     torch.manual_seed(11)
-    N, C, H, W = 8, 32, 16, 16
     x = torch.randn(N, C, H, W, device=DEV)
     bn = HipBatchNorm2d(C, momentum=0.1, eps=1e-3).to(DEV)
     ref = torch.nn.BatchNorm2d(C, momentum=0.1, eps=1e-3).to(DEV)
