@@ -7,6 +7,7 @@
 void gemm_nt_bf16(const at::Tensor& A, const at::Tensor& B, at::Tensor& C,
                   const c10::optional<at::Tensor>& bias, int64_t act,
                   double dropout_p, const c10::optional<at::Tensor>& seed);
+void conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3, at::Tensor& dw);
 void gemm_nt_bf16_probe(const at::Tensor& A, const at::Tensor& B,
                         at::Tensor& C, int64_t variant);
 void gemm_nt8(const at::Tensor& A, const at::Tensor& B, at::Tensor& C,
@@ -142,6 +143,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("A"), py::arg("B"), py::arg("C"), py::arg("bias"),
         py::arg("act"), py::arg("dropout_p") = 0.0,
         py::arg("seed") = c10::nullopt);
+  m.def("conv1x1_dw", &conv1x1_dw,
+        "dw[Co,Ci] = sum_b dy3[b] @ x3[b]^T read straight from [B,C,HW]",
+        py::arg("dy3"), py::arg("x3"), py::arg("dw"));
   m.def("gemm_nt_bf16_probe", &gemm_nt_bf16_probe);
   m.def("gemm_nt8", &gemm_nt8,
         "8-phase deep-pipelined GEMM (256^2-class tiles)");

@@ -258,6 +258,149 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_wave_kernel(
   }
 }
 
+// Pointwise-conv weight gradient straight from NCHW activations:
+//   dW[Co,Ci] = sum_b dy_b[Co,HW] * x_b[Ci,HW]^T,   dy [B,Co,HW], x [B,Ci,HW].
+// Both operands are already K-minor inside an image; the reduction index
+// k = b*HW + hw is only SEGMENTED by image: element (row, k) of the logical
+// [C, B*HW] operand lives at (b*C + row)*HW + hw. With 8 | HW every 16 B
+// lane load (8 consecutive k) lies inside one image, so a 32-wide K tile
+// may straddle images and is still staged with global_load_lds, one
+// (b, hw) per lane chunk — no channel-major permute copies.
+//
+// Work split: the output is 1-8 tiles of 64^2 and K is up to ~262k, so the
+// grid is (tiles x ksplit) workgroups of 4 waves (2x2, 32x32 per wave);
+// each owns K-tiles [split*per, split*per + per) of one output tile and
+// writes its fp32 partial into its OWN slot of C32 [ksplit][Co][Ci] (no
+// atomics; the slot epilogues above sum them in fixed order). Within a
+// slot k ascends in 32-wide MFMA steps, exactly as the split-K branch of
+// gemm_nt_bf16 does on the copied operands, so with the same partition the
+// result is bit-identical to the copy path. ksplit == 1 writes bf16 directly.
+//
+// Staging: one 1 KiB global_load_lds per wave per operand per K-tile (16
+// rows x 32 k). A lane's row never changes, so it carries one element
+// offset per operand plus its hw, and advances them by adds only: 32 k
+// forward is (32 / HW) whole images plus 32 % HW, with one conditional
+// wrap into the next image. No divide in the K loop.
+template <bool SPLITK>
+__global__ __launch_bounds__(256, 6) void conv1x1_dw_kernel(
+    const bf16_t* __restrict__ DY, const bf16_t* __restrict__ X,
+    bf16_t* __restrict__ DW, float* __restrict__ C32, int Co, int Ci, int HW,
+    int K, int lddw, int mtiles, int ntiles, int ksplit) {
+  constexpr int BT = 64, KSTEP = 32;
+  __shared__ bf16_t As[2][BT * KSTEP];
+  __shared__ bf16_t Bs[2][BT * KSTEP];
+
+  // Bijective XCD-aware swizzle, as gemm_nt_bf16_kernel: the tiles of one
+  // K slab are neighbours on one XCD and share its L2.
+  const int tiles = mtiles * ntiles;
+  const int nwg = tiles * ksplit;
+  const int orig = blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
+  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) +
+                 (orig >> 3);
+  const int split = wg / tiles;
+  const int tile_lin = wg % tiles;
+  const int row0 = (tile_lin / ntiles) * BT;
+  const int col0 = (tile_lin % ntiles) * BT;
+
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
+  const int wm = wid >> 1, wn = wid & 1;
+
+  const int ktiles = K / KSTEP;
+  const int per = (ktiles + ksplit - 1) / ksplit;
+  const int kt0 = split * per;
+  const int ktend = min(ktiles, kt0 + per);
+  if (kt0 >= ktend) return;  // host clamps ksplit so that this never hits
+
+  // This lane's chunk: row wid*16 + lane/4 of the tile (clamped; masked on
+  // store), k = kt*32 + (lane%4)*8.
+  const int srow = wid * 16 + (lane >> 2);
+  const int arow_g = min(row0 + srow, Co - 1);
+  const int brow_g = min(col0 + srow, Ci - 1);
+  const int kfirst = kt0 * KSTEP + (lane & 3) * 8;
+  const int img = kfirst / HW;
+  int hw = kfirst - img * HW;
+  int64_t offa = ((int64_t)img * Co + arow_g) * HW + hw;
+  int64_t offb = ((int64_t)img * Ci + brow_g) * HW + hw;
+  const int step_img = KSTEP / HW, step_hw = KSTEP % HW;
+  const int64_t stepa = (int64_t)step_img * Co * HW + step_hw;
+  const int64_t stepb = (int64_t)step_img * Ci * HW + step_hw;
+  const int64_t wrapa = (int64_t)(Co - 1) * HW;
+  const int64_t wrapb = (int64_t)(Ci - 1) * HW;
+
+  auto stage = [&](int b) {
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)(DY + offa),
+        (__attribute__((address_space(3))) void*)(As[b] + wid * 16 * KSTEP),
+        16, 0, 0);
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)(X + offb),
+        (__attribute__((address_space(3))) void*)(Bs[b] + wid * 16 * KSTEP),
+        16, 0, 0);
+    offa += stepa;
+    offb += stepb;
+    hw += step_hw;
+    if (hw >= HW) {  // crossed into the next image
+      hw -= HW;
+      offa += wrapa;
+      offb += wrapb;
+    }
+  };
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  stage(0);
+  int buf = 0;
+  for (int kt = kt0; kt < ktend; ++kt) {
+    // Per-wave drain of the LDS-DMA, then the barrier (see
+    // gemm_nt_bf16_kernel).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (kt + 1 < ktend) stage(buf ^ 1);
+    frag_ab a[2], b[2];
+    const int kofs = (lane >> 4) * 8;
+    const int arow = wm * 32 + (lane & 15);
+    const int brow = wn * 32 + (lane & 15);
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      a[f] = *(const frag_ab*)&As[buf][(arow + f * 16) * KSTEP + kofs];
+      b[f] = *(const frag_ab*)&Bs[buf][(brow + f * 16) * KSTEP + kofs];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a[i], b[j], acc[i][j], 0, 0, 0);
+    buf ^= 1;
+  }
+
+  // C/D layout (16x16x32): col = lane&15, row = (lane>>4)*4 + reg.
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int col = col0 + wn * 32 + j * 16 + (lane & 15);
+      if (col >= Ci) continue;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int row = row0 + wm * 32 + i * 16 + (lane >> 4) * 4 + rr;
+        if (row >= Co) continue;
+        if (SPLITK)
+          C32[((int64_t)split * Co + row) * Ci + col] = acc[i][j][rr];
+        else
+          DW[(int64_t)row * lddw + col] = f2bf(acc[i][j][rr]);
+      }
+    }
+  }
+}
+
 // GEMV path for skinny-M GEMMs (M <= 8: batch-1/small-batch serving,
 // where an MFMA tile would waste 63/64 rows): one wave per output column,
 // lanes stride K with 16 B loads, wave-shuffle reduction. Bandwidth-bound
@@ -385,6 +528,37 @@ __global__ void gemm_nt_generic_kernel(const bf16_t* __restrict__ A,
   }
 }
 
+// Sum the ksplit fp32 slots of C32 into bf16 C: a wave per element once the
+// slots outnumber what one thread should walk serially.
+static void launch_splitk_epilogue(const float* c32, const float* bias_ptr,
+                                   bf16_t* c, int M, int N, int ldc, int act,
+                                   int ksplit, hipStream_t stream) {
+  const int64_t tot = (int64_t)M * N;
+  if (ksplit > 16) {
+    hipLaunchKernelGGL(gemm_splitk_epilogue_wave_kernel,
+                       dim3((unsigned)((tot + 3) / 4)), dim3(256), 0, stream,
+                       c32, bias_ptr, c, M, N, ldc, act, ksplit);
+  } else {
+    hipLaunchKernelGGL(gemm_splitk_epilogue_kernel,
+                       dim3((int)std::min<int64_t>((tot + 255) / 256, 2048)),
+                       dim3(256), 0, stream, c32, bias_ptr, c, M, N, ldc, act,
+                       ksplit);
+  }
+}
+
+// The split-K partition of a K-dominant tiny-output GEMM: ~512 workgroups
+// over t64 output tiles, at least 256 k per split, then clamped so every
+// split owns >=1 K-tile: an empty split would leave its C32 slot UNWRITTEN
+// and the epilogue would sum garbage (observed as the NASNet 1x1 dW
+// nondeterminism, benchmarks/nas_det_probe.py).
+static int splitk_partition(int64_t t64, int K) {
+  int ksplit = (int)std::min<int64_t>(512 / t64, (int64_t)K / 256);
+  if (ksplit < 1) ksplit = 1;
+  const int ktiles = K / 32;
+  const int per = (ktiles + ksplit - 1) / ksplit;
+  return (ktiles + per - 1) / per;
+}
+
 void gemm_nt_bf16(const at::Tensor& A, const at::Tensor& B, at::Tensor& C,
                   const c10::optional<at::Tensor>& bias, int64_t act,
                   double dropout_p, const c10::optional<at::Tensor>& seed) {
@@ -454,37 +628,16 @@ void gemm_nt_bf16(const at::Tensor& A, const at::Tensor& B, at::Tensor& C,
       (t64 <= 256 && K >= 4096 && (int64_t)K >= 4 * std::max(M, N));
   if (fast && act != 3 && k_dominant &&
       std::min<int64_t>(512 / t64, (int64_t)K / 256) >= 2) {
-    int ksplit = (int)std::min<int64_t>(512 / t64, (int64_t)K / 256);
-    if (ksplit < 2) ksplit = 2;
-    // Clamp so every split owns >=1 K-tile: an empty split would leave its
-    // C32 slot UNWRITTEN and the epilogue would sum garbage (observed as
-    // the NASNet 1x1 dW nondeterminism, benchmarks/nas_det_probe.py).
-    {
-      const int ktiles = K / 32;
-      const int per = (ktiles + ksplit - 1) / ksplit;
-      ksplit = (ktiles + per - 1) / per;
-      if (ksplit < 2) ksplit = 2;
-    }
+    // >= 2 here: the branch needs min(512/t64, K/256) >= 2 and K >= 2048.
+    const int ksplit = splitk_partition(t64, K);
     auto C32 = at::empty({ksplit, M, N}, A.options().dtype(at::kFloat));
     const int mt = (M + 63) / 64, nt = (N + 63) / 64;
     hipLaunchKernelGGL((gemm_nt_bf16_kernel<64, 64, 2, 2, 6, 32, true>),
                        dim3(mt * nt * ksplit), dim3(THREADS), 0,
                        stream.stream(), a, b, c, nullptr, M, N, K, lda, ldb,
                        ldc, (int)act, mt, nt, C32.data_ptr<float>(), ksplit);
-    const int64_t tot = (int64_t)M * N;
-    if (ksplit > 16) {
-      hipLaunchKernelGGL(gemm_splitk_epilogue_wave_kernel,
-                         dim3((unsigned)((tot + 3) / 4)), dim3(256), 0,
-                         stream.stream(), C32.data_ptr<float>(), bias_ptr, c,
-                         M, N, ldc, (int)act, ksplit);
-    } else {
-      hipLaunchKernelGGL(gemm_splitk_epilogue_kernel,
-                         dim3((int)std::min<int64_t>((tot + 255) / 256,
-                                                     2048)),
-                         dim3(256), 0, stream.stream(),
-                         C32.data_ptr<float>(), bias_ptr, c, M, N, ldc,
-                         (int)act, ksplit);
-    }
+    launch_splitk_epilogue(C32.data_ptr<float>(), bias_ptr, c, M, N, ldc,
+                           (int)act, ksplit, stream.stream());
     HIP_CHECK_KERNEL();
     return;
   }
@@ -553,6 +706,62 @@ void gemm_nt_bf16(const at::Tensor& A, const at::Tensor& B, at::Tensor& C,
     hipLaunchKernelGGL(gemm_nt_generic_kernel, dim3(blocks), dim3(256), 0,
                        stream.stream(), a, b, c, bias_ptr, M, N, K, lda, ldb,
                        ldc, (int)act, seed_ptr, pthresh, inv_keep);
+  }
+  HIP_CHECK_KERNEL();
+}
+
+// dw[Co,Ci] = sum_b dy3[b] @ x3[b]^T for contiguous dy3 [B,Co,HW] and
+// x3 [B,Ci,HW]; dw is overwritten, its row stride honoured. Contract:
+// HW % 8 == 0 and (B*HW) % 32 == 0 (callers take the permute-copy +
+// gemm_nt_bf16 path otherwise). The K partition is gemm_nt_bf16's, so where
+// that takes its split-K branch for (Co, Ci, B*HW) the two agree bit for bit.
+void conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3, at::Tensor& dw) {
+  TORCH_CHECK(dy3.is_cuda() && x3.is_cuda() && dw.is_cuda(),
+              "conv1x1_dw: need GPU tensors");
+  TORCH_CHECK(dy3.get_device() == x3.get_device() &&
+              dy3.get_device() == dw.get_device(),
+              "conv1x1_dw: tensors on different devices");
+  TORCH_CHECK(dy3.scalar_type() == at::kBFloat16 &&
+              x3.scalar_type() == at::kBFloat16 &&
+              dw.scalar_type() == at::kBFloat16, "conv1x1_dw: bf16 required");
+  TORCH_CHECK(dy3.dim() == 3 && x3.dim() == 3 && dw.dim() == 2,
+              "conv1x1_dw: dy3 [B,Co,HW], x3 [B,Ci,HW], dw [Co,Ci]");
+  TORCH_CHECK(dy3.is_contiguous() && x3.is_contiguous(),
+              "conv1x1_dw: dy3 and x3 must be contiguous");
+  const int64_t B = dy3.size(0), Co = dy3.size(1), HW = dy3.size(2);
+  const int64_t Ci = x3.size(1);
+  TORCH_CHECK(x3.size(0) == B && x3.size(2) == HW,
+              "conv1x1_dw: dy3 and x3 disagree on B or HW");
+  TORCH_CHECK(dw.size(0) == Co && dw.size(1) == Ci && dw.stride(1) == 1,
+              "conv1x1_dw: dw must be [Co,Ci] with contiguous rows");
+  TORCH_CHECK(HW % 8 == 0 && (B * HW) % 32 == 0,
+              "conv1x1_dw: needs HW % 8 == 0 and (B*HW) % 32 == 0");
+  TORCH_CHECK(B * HW < (int64_t)1 << 31 && Co < (1 << 24) && Ci < (1 << 24),
+              "conv1x1_dw: shape out of range");
+  if (Co == 0 || Ci == 0) return;
+  if (B * HW == 0) { dw.zero_(); return; }
+  const int K = (int)(B * HW);
+  const int mt = (int)((Co + 63) / 64), nt = (int)((Ci + 63) / 64);
+  const int ksplit = splitk_partition((int64_t)mt * nt, K);
+  TORCH_CHECK((int64_t)mt * nt * ksplit < (int64_t)1 << 31,
+              "conv1x1_dw: grid out of range");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const bf16_t* dy = (const bf16_t*)dy3.data_ptr();
+  const bf16_t* x = (const bf16_t*)x3.data_ptr();
+  bf16_t* out = (bf16_t*)dw.data_ptr();
+  const int lddw = (int)dw.stride(0);
+  if (ksplit == 1) {
+    hipLaunchKernelGGL((conv1x1_dw_kernel<false>), dim3(mt * nt), dim3(256),
+                       0, stream.stream(), dy, x, out, nullptr, (int)Co,
+                       (int)Ci, (int)HW, K, lddw, mt, nt, 1);
+  } else {
+    auto C32 = at::empty({ksplit, Co, Ci}, dy3.options().dtype(at::kFloat));
+    hipLaunchKernelGGL((conv1x1_dw_kernel<true>), dim3(mt * nt * ksplit),
+                       dim3(256), 0, stream.stream(), dy, x, out,
+                       C32.data_ptr<float>(), (int)Co, (int)Ci, (int)HW, K,
+                       lddw, mt, nt, ksplit);
+    launch_splitk_epilogue(C32.data_ptr<float>(), nullptr, out, (int)Co,
+                           (int)Ci, lddw, 0, ksplit, stream.stream());
   }
   HIP_CHECK_KERNEL();
 }

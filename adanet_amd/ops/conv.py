@@ -7,12 +7,16 @@ nasnet.py ReluConvBN usage). On MI355X a pointwise conv IS a batched GEMM:
 
     y_b[Co, HW] = W[Co, Ci] @ x_b[Ci, HW]          (forward: trans_b staging)
     dX_b        = W^T @ dz_b                       (tt staging)
-    dW          = sum_b dz_b @ x_b^T               (NT over [C, B*HW] views)
+    dW          = sum_b dz_b @ x_b^T               (split-K over k = b*HW + hw)
 
 so csrc/gemm_tn.hip's gemm_tr_batched (grid.z = image) runs it on MFMA with
-zero im2col and zero transpose copies for fwd/dX. The fast path needs the
-GEMM alignment contract (Ci % 32 == 0, HW % 8 == 0); `conv1x1` falls back
-to torch's conv (MIOpen) otherwise, so arbitrary channel counts still work.
+zero im2col and zero transpose copies for fwd/dX, and csrc/gemm.hip's
+conv1x1_dw reads dz and x for dW where they lie in [B, C, HW] (needs
+HW % 8 == 0 and B*HW % 32 == 0; other shapes, and ADANET_CONV_DW_DIRECT=0,
+make two channel-major permute copies and call gemm_nt_bf16 — bit-identical
+where that GEMM splits K). The fast path needs the GEMM alignment contract
+(Ci % 32 == 0, HW % 8 == 0); `conv1x1` falls back to torch's conv (MIOpen)
+otherwise, so arbitrary channel counts still work.
 """
 
 from __future__ import annotations
@@ -36,6 +40,46 @@ def _aligned(x: torch.Tensor, co: int, ci: int) -> bool:
         return False
     hw = x.shape[2] * x.shape[3]
     return ci % 32 == 0 and co % 32 == 0 and hw % 8 == 0 and x.is_contiguous()
+
+
+def _dw_direct_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_CONV_DW_DIRECT", "1") != "0"
+
+
+def _weight_grad(dy3: torch.Tensor, x3: torch.Tensor) -> torch.Tensor:
+    """dW[Co, Ci] = sum_b dy3[b] @ x3[b]^T for contiguous bf16 [B, C, HW]."""
+    ext = _extension.require()
+    B, Co, HW = dy3.shape
+    Ci = x3.shape[1]
+    dw = torch.empty((Co, Ci), device=dy3.device, dtype=torch.bfloat16)
+    if _dw_direct_enabled() and HW % 8 == 0 and (B * HW) % 32 == 0:
+        ext.conv1x1_dw(dy3, x3, dw)
+    else:
+        # Copy path: channel-major [C, B*HW] operands, one permute copy each.
+        dz_flat = dy3.permute(1, 0, 2).reshape(Co, B * HW).contiguous()
+        x_flat = x3.permute(1, 0, 2).reshape(Ci, B * HW).contiguous()
+        ext.gemm_nt_bf16(dz_flat, x_flat, dw, None, 0)
+    return dw
+
+
+def conv1x1_weight_grad(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """Weight gradient of a 1x1 conv: dy [B, Co, H, W], x [B, Ci, H, W]
+    -> dW [Co, Ci] = sum over b, h, w of dy[b, :, h, w] x[b, :, h, w]^T.
+
+    bf16 GPU tensors run on the MFMA kernels; CPU tensors use an einsum.
+    """
+    if dy.dim() != 4 or x.dim() != 4 or dy.shape[0] != x.shape[0] \
+            or dy.shape[2:] != x.shape[2:]:
+        raise ValueError("conv1x1_weight_grad: dy [B,Co,H,W] and x "
+                         "[B,Ci,H,W] must agree on B, H, W")
+    if not dy.is_cuda:
+        return torch.einsum("bohw,bihw->oi", dy, x)
+    if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16:
+        raise TypeError("conv1x1_weight_grad: GPU tensors must be bf16")
+    B, Co, H, W = dy.shape
+    return _weight_grad(dy.contiguous().reshape(B, Co, H * W),
+                        x.contiguous().reshape(B, x.shape[1], H * W))
 
 
 class _Conv1x1Fn(torch.autograd.Function):
@@ -72,14 +116,9 @@ class _Conv1x1Fn(torch.autograd.Function):
             ext.gemm_tr_batched(weight, dy3, dx, None, 0, 1, 1)
             dx = dx.reshape(B, Ci, H, W)
         if ctx.needs_input_grad[1]:
-            # dW[Co, Ci] = dz_all[Co, B*HW] @ x_all[Ci, B*HW]^T — channel-
-            # major views need one permute copy each (conv is off the
-            # headline hot path; the GEMM itself runs on MFMA).
-            dz_flat = dy3.permute(1, 0, 2).reshape(Co, B * H * W).contiguous()
-            x_flat = x.reshape(B, Ci, H * W).permute(1, 0, 2).reshape(
-                Ci, B * H * W).contiguous()
-            dw = torch.empty((Co, Ci), device=x.device, dtype=torch.bfloat16)
-            ext.gemm_nt_bf16(dz_flat, x_flat, dw, None, 0)
+            # dW[Co, Ci] = dz_all[Co, B*HW] @ x_all[Ci, B*HW]^T, read from
+            # the [B, C, HW] layout directly when the shape allows it.
+            dw = _weight_grad(dy3, x.reshape(B, Ci, H * W))
         if ctx.has_bias:
             db = dy3.sum(dim=(0, 2)).float()
         return dx, dw, db
