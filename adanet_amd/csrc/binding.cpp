@@ -112,6 +112,15 @@ void depthwise_bwd_dx(const at::Tensor& dy, const at::Tensor& w,
                       at::Tensor& dx, int64_t stride, int64_t pad);
 void depthwise_bwd_dw(const at::Tensor& x, const at::Tensor& dy,
                       at::Tensor& dw, int64_t stride, int64_t pad);
+bool sepconv_infer_supported(int64_t Ci, int64_t Co, int64_t H, int64_t W,
+                             int64_t K, int64_t stride, int64_t pad);
+void sepconv_infer(const at::Tensor& x, const c10::optional<at::Tensor>& dw_w,
+                   const at::Tensor& pw_w,
+                   const c10::optional<at::Tensor>& mean,
+                   const c10::optional<at::Tensor>& rstd,
+                   const c10::optional<at::Tensor>& gamma,
+                   const c10::optional<at::Tensor>& beta, at::Tensor& y,
+                   int64_t stride, int64_t pad);
 void argmax_correct(const at::Tensor& logits, const at::Tensor& labels,
                     const c10::optional<at::Tensor>& pred, at::Tensor& correct);
 void im2col_bf16(const at::Tensor& x, at::Tensor& out, int64_t K,
@@ -219,4 +228,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("depthwise_fwd", &depthwise_fwd);
   m.def("depthwise_bwd_dx", &depthwise_bwd_dx);
   m.def("depthwise_bwd_dw", &depthwise_bwd_dw);
+  m.def("sepconv_infer", &sepconv_infer,
+        "fused eval-mode relu -> depthwise KxK -> pointwise -> BatchNorm; "
+        "dw_w=None skips the depthwise stage, mean=None skips BatchNorm",
+        py::arg("x"), py::arg("dw_w"), py::arg("pw_w"), py::arg("mean"),
+        py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("y"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("sepconv_infer_supported", &sepconv_infer_supported,
+        "whether sepconv_infer has a kernel for the shape (K = 1: no "
+        "depthwise stage)",
+        py::arg("Ci"), py::arg("Co"), py::arg("H"), py::arg("W"),
+        py::arg("K"), py::arg("stride"), py::arg("pad"));
 }

@@ -61,6 +61,15 @@ def drop_path(x, keep_prob: float, training: bool):
     return x if scale is None else x * scale
 
 
+def _fused_infer(module: nn.Module, x: torch.Tensor) -> bool:
+    """Whether a conv stack may run on the forward-only fused kernel
+    (ops/conv.py sepconv_bn_infer): eval mode, no autograd, GPU input, and
+    ADANET_FUSED_SEPCONV not 0."""
+    from adanet_amd.ops.conv import _fused_sepconv_enabled
+    return (not module.training and not torch.is_grad_enabled()
+            and x.is_cuda and _fused_sepconv_enabled())
+
+
 class SepConv(nn.Module):
     """Two stacked depthwise-separable convs, each ReLU->dw->pw->BN
     (reference _stacked_separable_conv, nasnet_utils.py:182-248)."""
@@ -84,6 +93,15 @@ class SepConv(nn.Module):
         )
 
     def forward(self, x):
+        if _fused_infer(self, x):
+            # frozen members, the Evaluator and serving: one launch per
+            # ReLU-dw-pw-BN half (csrc/sepconv_infer.hip)
+            from adanet_amd.ops.conv import sepconv_bn_infer
+            for i in (0, 4):
+                dw, pw, bn = self.op[i + 1], self.op[i + 2], self.op[i + 3]
+                x = sepconv_bn_infer(x, dw.weight, pw.weight, bn.bn,
+                                     dw.stride, dw.padding)
+            return x
         return self.op(x)
 
 
@@ -104,6 +122,10 @@ class ReluConvBN(nn.Module):
         )
 
     def forward(self, x):
+        from adanet_amd.ops.conv import HipConv1x1, sepconv_bn_infer
+        if isinstance(self.op[1], HipConv1x1) and _fused_infer(self, x):
+            return sepconv_bn_infer(x, None, self.op[1].weight,
+                                    self.op[2].bn)
         return self.op(x)
 
 

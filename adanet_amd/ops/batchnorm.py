@@ -86,6 +86,14 @@ class HipBatchNorm2d(nn.Module):
             "num_batches_tracked", torch.zeros((), dtype=torch.long))
 
     def forward(self, x):
+        return self._run(x, self.training)
+
+    def infer(self, x):
+        """Normalise with the running statistics, whatever `self.training`
+        says: what `forward` does in eval mode."""
+        return self._run(x, False)
+
+    def _run(self, x, training):
         # dtype pinning: stats/affine are fp32 by design; a blanket
         # module.to(bf16) without restore_fp32_params must not break BN.
         if self.running_mean.dtype != torch.float32:
@@ -95,17 +103,17 @@ class HipBatchNorm2d(nn.Module):
             self.weight.data = self.weight.data.float()
             self.bias.data = self.bias.data.float()
         if x.is_cuda:
-            if self.training:
+            if training:
                 self.num_batches_tracked += 1
             return _BatchNormFn.apply(
                 x.to(torch.bfloat16), self.weight, self.bias,
                 self.running_mean, self.running_var, self.momentum, self.eps,
-                self.training)
+                training)
         out = F.batch_norm(
             x.float(), self.running_mean, self.running_var,
             self.weight.float() if self.weight is not None else None,
             self.bias.float() if self.bias is not None else None,
-            self.training, self.momentum, self.eps)
+            training, self.momentum, self.eps)
         return out.to(x.dtype)
 
     def extra_repr(self):

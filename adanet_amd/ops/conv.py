@@ -223,18 +223,109 @@ class HipDepthwiseConv2d(nn.Module):
         self.weight = nn.Parameter(ref.weight.detach())  # [C,1,K,K]
 
     def forward(self, x):
-        if (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
-                and self.weight.dtype == torch.bfloat16
-                and _native_enabled()):
-            return _DepthwiseFn.apply(x, self.weight.contiguous(),
-                                      self.stride, self.padding)
-        return torch.nn.functional.conv2d(
-            x, self.weight.to(x.dtype), None, self.stride, self.padding,
-            groups=self.channels)
+        return depthwise_conv2d(x, self.weight, self.stride, self.padding)
 
     def extra_repr(self):
         return "C=%d, k=%d, s=%d, p=%d (native bf16 path)" % (
             self.channels, self.kernel_size, self.stride, self.padding)
+
+
+def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1,
+                     padding: int = 0) -> torch.Tensor:
+    """Functional depthwise conv, weight [C, 1, K, K]: the native kernel for
+    contiguous bf16 GPU tensors, grouped conv2d otherwise."""
+    if (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and weight.dtype == torch.bfloat16 and _native_enabled()):
+        return _DepthwiseFn.apply(x, weight.contiguous(), stride, padding)
+    return torch.nn.functional.conv2d(
+        x, weight.to(x.dtype), None, stride, padding, groups=weight.shape[0])
+
+
+def _fused_sepconv_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_FUSED_SEPCONV", "1") != "0"
+
+
+def _bf16_dense(t: torch.Tensor) -> bool:
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()
+            and t.data_ptr() % 16 == 0)
+
+
+def sepconv_infer_supported(x: torch.Tensor,
+                            dw_weight: Optional[torch.Tensor],
+                            pw_weight: torch.Tensor, stride: int = 1,
+                            padding: int = 0) -> bool:
+    """Whether `sepconv_bn_infer` runs these arguments on the fused kernel
+    (csrc/sepconv_infer.hip) rather than on the four-launch chain."""
+    if x.dim() != 4 or not _bf16_dense(x) or not _bf16_dense(pw_weight) \
+            or not _native_enabled() or pw_weight.dim() not in (2, 4) \
+            or pw_weight.numel() != pw_weight.shape[0] * x.shape[1]:
+        return False
+    k = 1
+    if dw_weight is not None:
+        if not _bf16_dense(dw_weight) or dw_weight.dim() != 4 \
+                or dw_weight.shape[0] != x.shape[1] \
+                or dw_weight.shape[1] != 1 \
+                or dw_weight.shape[2] != dw_weight.shape[3]:
+            return False
+        k = dw_weight.shape[-1]
+        if k == 1:      # a 1x1 depthwise scales channels: not the K=1 form
+            return False
+    elif stride != 1 or padding != 0:
+        return False
+    _, ci, h, w = x.shape
+    return x.shape[0] <= 65535 and _extension.require(
+    ).sepconv_infer_supported(ci, pw_weight.shape[0], h, w, k, stride,
+                              padding)
+
+
+def sepconv_bn_infer(x: torch.Tensor, dw_weight: Optional[torch.Tensor],
+                     pw_weight: torch.Tensor, bn: Optional[nn.Module] = None,
+                     stride: int = 1, padding: int = 0) -> torch.Tensor:
+    """Inference-only ReLU -> depthwise KxK -> pointwise 1x1 -> BatchNorm
+    (running statistics) of one separable-conv half-stack.
+
+    x [B, Ci, H, W]; dw_weight [Ci, 1, K, K] or None for no depthwise stage
+    (ReLU-Conv-BN); pw_weight [Co, Ci] or [Co, Ci, 1, 1]; bn a
+    `HipBatchNorm2d` or None. bf16 GPU tensors of a supported shape
+    (`sepconv_infer_supported`) take one fused launch that rounds where the
+    chain of four kernels rounds; everything else, CPU tensors included,
+    runs that chain. There is no backward: tensors that require grad are
+    refused while grad mode is on.
+    """
+    if torch.is_grad_enabled():
+        params = [x, dw_weight, pw_weight]
+        if bn is not None:
+            params += [bn.weight, bn.bias]
+        if any(t is not None and t.requires_grad for t in params):
+            raise RuntimeError(
+                "sepconv_bn_infer has no backward: call it under "
+                "torch.no_grad() or with tensors that do not require grad")
+    if _fused_sepconv_enabled() and sepconv_infer_supported(
+            x, dw_weight, pw_weight, stride, padding):
+        ext = _extension.require()
+        B, _, H, W = x.shape
+        co = pw_weight.shape[0]
+        k = 1 if dw_weight is None else dw_weight.shape[-1]
+        oh = (H + 2 * padding - k) // stride + 1
+        ow = (W + 2 * padding - k) // stride + 1
+        y = torch.empty((B, co, oh, ow), device=x.device,
+                        dtype=torch.bfloat16)
+        mean = rstd = gamma = beta = None
+        if bn is not None:
+            mean = bn.running_mean.float()
+            rstd = (bn.running_var.float() + bn.eps).rsqrt()
+            if bn.weight is not None:
+                gamma = bn.weight.detach().float()
+                beta = bn.bias.detach().float()
+        ext.sepconv_infer(x, dw_weight, pw_weight, mean, rstd, gamma, beta,
+                          y, stride, padding)
+        return y
+    y = F.relu(x)
+    if dw_weight is not None:
+        y = depthwise_conv2d(y, dw_weight, stride, padding)
+    y = conv1x1(y, pw_weight)
+    return bn.infer(y) if bn is not None else y
 
 
 class _Im2colFn(torch.autograd.Function):

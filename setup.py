@@ -32,6 +32,7 @@ SRC = [
     "adanet_amd/csrc/reduce.hip",
     "adanet_amd/csrc/eval_metrics.hip",
     "adanet_amd/csrc/depthwise.hip",
+    "adanet_amd/csrc/sepconv_infer.hip",
 ]
 
 def _version():
