@@ -121,6 +121,19 @@ void sepconv_infer(const at::Tensor& x, const c10::optional<at::Tensor>& dw_w,
                    const c10::optional<at::Tensor>& gamma,
                    const c10::optional<at::Tensor>& beta, at::Tensor& y,
                    int64_t stride, int64_t pad);
+bool factred_supported(int64_t Ci, int64_t Co, int64_t H, int64_t W);
+void factred_fwd(const at::Tensor& x, const at::Tensor& w1,
+                 const at::Tensor& w2, const c10::optional<at::Tensor>& mean,
+                 const c10::optional<at::Tensor>& rstd,
+                 const c10::optional<at::Tensor>& gamma,
+                 const c10::optional<at::Tensor>& beta, at::Tensor& y);
+void factred_bwd_dx(const at::Tensor& dy, const at::Tensor& x,
+                    const at::Tensor& w1, const at::Tensor& w2,
+                    at::Tensor& dx);
+int64_t factred_dw_slots(int64_t B, int64_t Ci, int64_t H, int64_t W,
+                         int64_t split);
+void factred_bwd_dw(const at::Tensor& x, const at::Tensor& dy, at::Tensor& dw,
+                    at::Tensor& wsp, int64_t split);
 void argmax_correct(const at::Tensor& logits, const at::Tensor& labels,
                     const c10::optional<at::Tensor>& pred, at::Tensor& correct);
 void im2col_bf16(const at::Tensor& x, at::Tensor& out, int64_t K,
@@ -239,4 +252,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "depthwise stage)",
         py::arg("Ci"), py::arg("Co"), py::arg("H"), py::arg("W"),
         py::arg("K"), py::arg("stride"), py::arg("pad"));
+  m.def("factred_supported", &factred_supported,
+        "whether the factorized-reduction kernels take the shape",
+        py::arg("Ci"), py::arg("Co"), py::arg("H"), py::arg("W"));
+  m.def("factred_fwd", &factred_fwd,
+        "fused relu -> two offset stride-2 1x1 convs -> concat; mean=None "
+        "skips the eval-mode BatchNorm epilogue",
+        py::arg("x"), py::arg("w1"), py::arg("w2"), py::arg("mean"),
+        py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("y"));
+  m.def("factred_bwd_dx", &factred_bwd_dx,
+        "input gradient of factred_fwd, every dx element written once",
+        py::arg("dy"), py::arg("x"), py::arg("w1"), py::arg("w2"),
+        py::arg("dx"));
+  m.def("factred_dw_slots", &factred_dw_slots,
+        "workspace slots factred_bwd_dw writes for a requested split (0: "
+        "automatic)",
+        py::arg("B"), py::arg("Ci"), py::arg("H"), py::arg("W"),
+        py::arg("split") = 0);
+  m.def("factred_bwd_dw", &factred_bwd_dw,
+        "dw[Co,Ci] (dW1 above dW2) of factred_fwd: split-K partials into "
+        "wsp[slots,Co,Ci] fp32, then a fixed-order slot sum",
+        py::arg("x"), py::arg("dy"), py::arg("dw"), py::arg("wsp"),
+        py::arg("split") = 0);
 }

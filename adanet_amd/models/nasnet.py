@@ -70,6 +70,11 @@ def _fused_infer(module: nn.Module, x: torch.Tensor) -> bool:
             and x.is_cuda and _fused_sepconv_enabled())
 
 
+def _factred_train_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_FACTRED_TRAIN", "0") == "1"
+
+
 class SepConv(nn.Module):
     """Two stacked depthwise-separable convs, each ReLU->dw->pw->BN
     (reference _stacked_separable_conv, nasnet_utils.py:182-248)."""
@@ -131,7 +136,10 @@ class ReluConvBN(nn.Module):
 
 class FactorizedReduction(nn.Module):
     """Stride-2 reduction without information loss: two offset 1x1 paths
-    (reference nasnet_utils.py:94-135)."""
+    (reference nasnet_utils.py:94-135). Eval mode under no_grad runs one
+    fused launch for any filter count that is a multiple of 32
+    (ops/conv.py factorized_reduction_bn_infer); training keeps the chain
+    unless ADANET_FACTRED_TRAIN=1."""
 
     def __init__(self, c_in, c_out):
         super().__init__()
@@ -146,6 +154,20 @@ class FactorizedReduction(nn.Module):
         self.bn = BNfp32(c_out)
 
     def forward(self, x):
+        from adanet_amd.ops import conv
+        if _fused_infer(self, x) and conv._fused_factred_enabled():
+            # frozen members, the Evaluator and serving: the whole module
+            # in one launch (csrc/factred.hip); ADANET_FUSED_FACTRED=0
+            # restores the chain below
+            return conv.factorized_reduction_bn_infer(
+                x, self.p1.weight, self.p2.weight, self.bn.bn)
+        if x.is_cuda and _factred_train_enabled():
+            # Opt-in (ADANET_FACTRED_TRAIN=1): fused forward, dX and dW
+            # kernels under autograd. They round where the chain rounds but
+            # sum fp32 in another order, which selection amplifies
+            # (ARCHITECTURE.md, Determinism), so the default stays the chain.
+            return self.bn(conv.factorized_reduction(
+                x, self.p1.weight, self.p2.weight))
         x = self.relu(x)
         a = self.p1(x)
         b = self.p2(F.pad(x, (0, 1, 0, 1))[:, :, 1:, 1:])

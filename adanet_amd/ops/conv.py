@@ -381,33 +381,164 @@ class HipConvNxN(nn.Module):
             self.register_parameter("bias", None)
 
     def forward(self, x):
-        K = self.kernel_size
-        ckk = self.in_channels * K * K
-        ckk_pad = (ckk + 31) // 32 * 32
-        if (x.is_cuda and x.dtype == torch.bfloat16 and _native_enabled()
-                and self.weight.dtype == torch.bfloat16
-                and self.out_channels % 32 == 0):
-            B = x.shape[0]
-            oh = (x.shape[2] + 2 * self.padding - K) // self.stride + 1
-            ow = (x.shape[3] + 2 * self.padding - K) // self.stride + 1
-            # batched im2col with the 32-alignment zero-pad folded in
-            # (torch's F.unfold is one im2col launch PER IMAGE).
-            u = _Im2colFn.apply(x.contiguous(), K, self.stride,
-                                self.padding, ckk_pad, oh, ow)
-            w2 = self.weight.reshape(self.out_channels, ckk)
-            if ckk_pad != ckk:
-                w2 = torch.nn.functional.pad(w2, (0, ckk_pad - ckk))
-            y = _Conv1x1Fn.apply(u, w2.contiguous(), self.bias)
-            return y
-        return torch.nn.functional.conv2d(
-            x, self.weight.to(x.dtype),
-            self.bias.to(x.dtype) if self.bias is not None else None,
-            self.stride, self.padding)
+        return conv_nxn(x, self.weight, self.bias, self.stride, self.padding)
 
     def extra_repr(self):
         return "in=%d, out=%d, k=%d, s=%d (im2col+MFMA when Co%%32==0)" % (
             self.in_channels, self.out_channels, self.kernel_size,
             self.stride)
+
+
+def conv_nxn(x: torch.Tensor, weight: torch.Tensor,
+             bias: Optional[torch.Tensor] = None, stride: int = 1,
+             padding: int = 0) -> torch.Tensor:
+    """Functional `HipConvNxN`: weight [Co, Ci, K, K], bias fp32 [Co]."""
+    co, ci, K, _ = weight.shape
+    ckk = ci * K * K
+    ckk_pad = (ckk + 31) // 32 * 32
+    if (x.is_cuda and x.dtype == torch.bfloat16 and _native_enabled()
+            and weight.dtype == torch.bfloat16 and co % 32 == 0):
+        oh = (x.shape[2] + 2 * padding - K) // stride + 1
+        ow = (x.shape[3] + 2 * padding - K) // stride + 1
+        # batched im2col with the 32-alignment zero-pad folded in
+        # (torch's F.unfold is one im2col launch PER IMAGE).
+        u = _Im2colFn.apply(x.contiguous(), K, stride, padding, ckk_pad,
+                            oh, ow)
+        w2 = weight.reshape(co, ckk)
+        if ckk_pad != ckk:
+            w2 = torch.nn.functional.pad(w2, (0, ckk_pad - ckk))
+        return _Conv1x1Fn.apply(u, w2.contiguous(), bias)
+    return torch.nn.functional.conv2d(
+        x, weight.to(x.dtype),
+        bias.to(x.dtype) if bias is not None else None, stride, padding)
+
+
+def _fused_factred_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_FUSED_FACTRED", "1") != "0"
+
+
+def _factred_weights(w1: torch.Tensor, w2: torch.Tensor):
+    """Both halves as Conv2d-layout [Co/2, Ci, 1, 1] views."""
+    return tuple(w if w.dim() == 4 else w.reshape(w.shape[0], w.shape[1], 1, 1)
+                 for w in (w1, w2))
+
+
+def _factred_chain(x, w1, w2):
+    """The unfused composition: relu, the one-pixel shift by pad and slice,
+    two stride-2 1x1 convs, channel concat."""
+    w1, w2 = _factred_weights(w1, w2)
+    r = F.relu(x)
+    a = conv_nxn(r, w1, None, 2, 0)
+    b = conv_nxn(F.pad(r, (0, 1, 0, 1))[:, :, 1:, 1:], w2, None, 2, 0)
+    return torch.cat([a, b], dim=1)
+
+
+def factorized_reduction_supported(x: torch.Tensor, w1: torch.Tensor,
+                                   w2: torch.Tensor) -> bool:
+    """Whether `factorized_reduction` runs these arguments on the fused
+    kernels (csrc/factred.hip) rather than on the unfused composition."""
+    if x.dim() != 4 or not _native_enabled() or x.shape[0] > 65535 \
+            or not all(_bf16_dense(t) for t in (x, w1, w2)) \
+            or w1.shape != w2.shape or w1.dim() not in (2, 4) \
+            or w1.numel() != w1.shape[0] * x.shape[1]:
+        return False
+    _, ci, h, w = x.shape
+    return _extension.require().factred_supported(ci, 2 * w1.shape[0], h, w)
+
+
+def _factred_out(x, w1):
+    B, _, H, W = x.shape
+    return torch.empty((B, 2 * w1.shape[0], (H - 1) // 2 + 1,
+                        (W - 1) // 2 + 1), device=x.device,
+                       dtype=torch.bfloat16)
+
+
+class _FactRedFn(torch.autograd.Function):
+    """relu -> two offset stride-2 1x1 convs -> concat on csrc/factred.hip:
+    one launch forward, one for dX, one split-K launch plus the slot sum
+    for both weight gradients. Saves x and the weights only."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2):
+        y = _factred_out(x, w1)
+        _extension.require().factred_fwd(x, w1, w2, None, None, None, None, y)
+        ctx.save_for_backward(x, w1, w2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _extension.require()
+        x, w1, w2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw1 = dw2 = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            ext.factred_bwd_dx(dy, x, w1, w2, dx)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            B, ci, H, W = x.shape
+            ch = w1.shape[0]
+            slots = ext.factred_dw_slots(B, ci, H, W, 0)
+            wsp = torch.empty((slots, 2 * ch, ci), device=x.device,
+                              dtype=torch.float32)
+            dw = torch.empty((2 * ch, ci), device=x.device,
+                             dtype=torch.bfloat16)
+            ext.factred_bwd_dw(x, dy, dw, wsp, 0)
+            dw1, dw2 = dw[:ch].reshape(w1.shape), dw[ch:].reshape(w2.shape)
+        return dx, dw1, dw2
+
+
+def factorized_reduction(x: torch.Tensor, w1: torch.Tensor,
+                         w2: torch.Tensor) -> torch.Tensor:
+    """ReLU, then two stride-2 1x1 convs over the even and the odd pixel
+    lattice, concatenated: y[:, :Co/2, oh, ow] = w1 @ relu(x)[:, :, 2oh, 2ow]
+    and y[:, Co/2:, oh, ow] = w2 @ relu(x)[:, :, 2oh+1, 2ow+1] (zero where
+    that pixel lies outside). The part of NASNet's factorized reduction in
+    front of its BatchNorm.
+
+    x [B, Ci, H, W]; w1, w2 [Co/2, Ci] or [Co/2, Ci, 1, 1]. Returns
+    [B, Co, (H-1)//2+1, (W-1)//2+1]. Differentiable. bf16 GPU tensors of a
+    supported shape (`factorized_reduction_supported`) run three fused
+    kernels that round where the composition rounds; everything else, CPU
+    tensors and ADANET_NATIVE_CONV=0 included, runs the composition.
+    """
+    if factorized_reduction_supported(x, w1, w2):
+        return _FactRedFn.apply(x, w1, w2)
+    return _factred_chain(x, w1, w2)
+
+
+def factorized_reduction_bn_infer(x: torch.Tensor, w1: torch.Tensor,
+                                  w2: torch.Tensor,
+                                  bn: Optional[nn.Module] = None
+                                  ) -> torch.Tensor:
+    """Inference-only `factorized_reduction` followed by BatchNorm on the
+    running statistics of `bn` (a `HipBatchNorm2d`, or None): one launch
+    where supported, otherwise the composition and `bn.infer`. There is no
+    backward: tensors that require grad are refused while grad mode is on.
+    """
+    if torch.is_grad_enabled():
+        params = [x, w1, w2]
+        if bn is not None:
+            params += [bn.weight, bn.bias]
+        if any(t is not None and t.requires_grad for t in params):
+            raise RuntimeError(
+                "factorized_reduction_bn_infer has no backward: call it "
+                "under torch.no_grad() or with tensors that do not require "
+                "grad")
+    if _fused_factred_enabled() and factorized_reduction_supported(x, w1, w2):
+        y = _factred_out(x, w1)
+        mean = rstd = gamma = beta = None
+        if bn is not None:
+            mean = bn.running_mean.float()
+            rstd = (bn.running_var.float() + bn.eps).rsqrt()
+            if bn.weight is not None:
+                gamma = bn.weight.detach().float()
+                beta = bn.bias.detach().float()
+        _extension.require().factred_fwd(x, w1, w2, mean, rstd, gamma, beta,
+                                         y)
+        return y
+    y = _factred_chain(x, w1, w2)
+    return bn.infer(y) if bn is not None else y
 
 
 class _Pool3Fn(torch.autograd.Function):

@@ -33,6 +33,7 @@ SRC = [
     "adanet_amd/csrc/eval_metrics.hip",
     "adanet_amd/csrc/depthwise.hip",
     "adanet_amd/csrc/sepconv_infer.hip",
+    "adanet_amd/csrc/factred.hip",
 ]
 
 def _version():
