@@ -134,6 +134,15 @@ int64_t factred_dw_slots(int64_t B, int64_t Ci, int64_t H, int64_t W,
                          int64_t split);
 void factred_bwd_dw(const at::Tensor& x, const at::Tensor& dy, at::Tensor& dw,
                     at::Tensor& wsp, int64_t split);
+bool relu_depthwise_supported(int64_t C, int64_t H, int64_t W, int64_t KS,
+                              int64_t stride, int64_t pad);
+void relu_depthwise_fwd(const at::Tensor& x, const at::Tensor& w,
+                        at::Tensor& y, int64_t stride, int64_t pad);
+void relu_depthwise_bwd(const at::Tensor& x, const at::Tensor& dy,
+                        const at::Tensor& w,
+                        const c10::optional<at::Tensor>& dx,
+                        const c10::optional<at::Tensor>& dw, int64_t stride,
+                        int64_t pad);
 void argmax_correct(const at::Tensor& logits, const at::Tensor& labels,
                     const c10::optional<at::Tensor>& pred, at::Tensor& correct);
 void im2col_bf16(const at::Tensor& x, at::Tensor& out, int64_t K,
@@ -274,4 +283,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "wsp[slots,Co,Ci] fp32, then a fixed-order slot sum",
         py::arg("x"), py::arg("dy"), py::arg("dw"), py::arg("wsp"),
         py::arg("split") = 0);
+  m.def("relu_depthwise_supported", &relu_depthwise_supported,
+        "whether the fused relu -> depthwise kernels take the shape",
+        py::arg("C"), py::arg("H"), py::arg("W"), py::arg("KS"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("relu_depthwise_fwd", &relu_depthwise_fwd,
+        "y = depthwise(relu(x)), relu(x) never written to memory",
+        py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stride"),
+        py::arg("pad"));
+  m.def("relu_depthwise_bwd", &relu_depthwise_bwd,
+        "backward of relu_depthwise_fwd in one launch plus the slot sum: dx "
+        "bf16 like x (masked by x > 0), dw fp32 [C*KS*KS]; None skips that "
+        "half and leaves it untouched",
+        py::arg("x"), py::arg("dy"), py::arg("w"), py::arg("dx"),
+        py::arg("dw"), py::arg("stride"), py::arg("pad"));
 }

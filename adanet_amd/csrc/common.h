@@ -58,20 +58,28 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 
 // Sum each acc[t] over the 256-thread block; thread 0 hands the total to
 // emit(t, total). The barrier after the emit frees the LDS scratch for the
-// next t and for whatever the caller does next.
-template <int N, typename Emit>
+// next t and for whatever the caller does next. `sync` is the block barrier:
+// a file built without some target features passes its own, because the
+// runtime header's __syncthreads is not inlined into such code.
+template <int N, typename Emit, typename Sync>
 __device__ __forceinline__ void block_reduce_sum(const float (&acc)[N],
-                                                 Emit emit) {
+                                                 Emit emit, Sync sync) {
   __shared__ float partial[4];
 #pragma unroll
   for (int t = 0; t < N; ++t) {
     const float v = wave_reduce_sum(acc[t]);
     if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = v;
-    __syncthreads();
+    sync();
     if (threadIdx.x == 0)
       emit(t, partial[0] + partial[1] + partial[2] + partial[3]);
-    __syncthreads();
+    sync();
   }
+}
+
+template <int N, typename Emit>
+__device__ __forceinline__ void block_reduce_sum(const float (&acc)[N],
+                                                 Emit emit) {
+  block_reduce_sum(acc, emit, [] { __syncthreads(); });
 }
 
 // One wave's sum of the n slots base[r * stride]: lane l takes

@@ -107,7 +107,16 @@ class SepConv(nn.Module):
                 x = sepconv_bn_infer(x, dw.weight, pw.weight, bn.bn,
                                      dw.stride, dw.padding)
             return x
-        return self.op(x)
+        # training: the ReLU rides inside the depthwise kernels where they
+        # support the shape (csrc/relu_depthwise.hip, bit-identical to the
+        # two modules), so no relu(x) is kept for backward. self.op[0] and
+        # self.op[4] stay in the Sequential for the state-dict indices.
+        from adanet_amd.ops.conv import relu_depthwise_conv2d
+        for i in (0, 4):
+            dw, pw, bn = self.op[i + 1], self.op[i + 2], self.op[i + 3]
+            x = bn(pw(relu_depthwise_conv2d(x, dw.weight, dw.stride,
+                                            dw.padding)))
+        return x
 
 
 class ReluConvBN(nn.Module):

@@ -241,6 +241,90 @@ def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1,
         x, weight.to(x.dtype), None, stride, padding, groups=weight.shape[0])
 
 
+def _fused_relu_dw_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_FUSED_RELU_DW", "1") != "0"
+
+
+def _relu_dw_pays(h: int, w: int, k: int) -> bool:
+    """The part of the kernels' class where both fused directions measured
+    no slower than the chain (BENCHMARKS.md, "Fused ReLU -> depthwise"): at
+    most 2304 tap products per input plane, that is 16x16 with 3x3 taps and
+    8x8 with 3x3 or 5x5. Above it the one-launch backward loses to the
+    separate dW and dX kernels (32x32 5x5: 183 us against 150), so those
+    shapes keep the chain."""
+    return h * w * k * k <= 2304
+
+
+def relu_depthwise_supported(x: torch.Tensor, weight: torch.Tensor,
+                             stride: int = 1, padding: int = 0) -> bool:
+    """Whether `relu_depthwise_conv2d` runs these arguments on the fused
+    kernels (csrc/relu_depthwise.hip) rather than on relu then
+    `depthwise_conv2d`: the kernels must take them and must have measured
+    no slower than the chain at that size (`_relu_dw_pays`)."""
+    if x.dim() != 4 or weight.dim() != 4 or not _native_enabled() \
+            or not _fused_relu_dw_enabled() \
+            or not (x.is_cuda and x.dtype == torch.bfloat16
+                    and x.is_contiguous() and x.data_ptr() % 16 == 0) \
+            or not (weight.is_cuda and weight.dtype == torch.bfloat16) \
+            or weight.shape[0] != x.shape[1] or weight.shape[1] != 1 \
+            or weight.shape[2] != weight.shape[3] or x.numel() == 0:
+        return False
+    _, c, h, w = x.shape
+    k = weight.shape[-1]
+    return _relu_dw_pays(h, w, k) and _extension.require(
+    ).relu_depthwise_supported(c, h, w, k, stride, padding)
+
+
+class _ReluDepthwiseFn(torch.autograd.Function):
+    """relu -> depthwise KxK on csrc/relu_depthwise.hip: one launch forward,
+    one launch plus the slot sum for dX and dW together. Saves x and the
+    weight only; relu(x) never exists in memory."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, pad):
+        B, C, H, W = x.shape
+        KS = weight.shape[-1]
+        y = torch.empty((B, C, (H + 2 * pad - KS) // stride + 1,
+                         (W + 2 * pad - KS) // stride + 1), device=x.device,
+                        dtype=torch.bfloat16)
+        _extension.require().relu_depthwise_fwd(x, weight, y, stride, pad)
+        ctx.save_for_backward(x, weight)
+        ctx.stride, ctx.pad = stride, pad
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dx = dwf = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+        if ctx.needs_input_grad[1]:
+            dwf = torch.empty(weight.numel(), device=x.device,
+                              dtype=torch.float32)
+        _extension.require().relu_depthwise_bwd(
+            x, dy.contiguous(), weight, dx, dwf, ctx.stride, ctx.pad)
+        if dwf is not None:
+            dw = dwf.reshape(weight.shape).to(weight.dtype)
+        return dx, dw, None, None
+
+
+def relu_depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor,
+                          stride: int = 1, padding: int = 0) -> torch.Tensor:
+    """depthwise_conv2d(relu(x), weight, stride, padding), weight
+    [C, 1, K, K]. Differentiable. Contiguous bf16 GPU tensors with K in
+    {3, 5, 7}, stride 1 or 2 and H*W*K*K <= 2304, the sizes at which they
+    measured no slower (`relu_depthwise_supported`), run the fused kernels,
+    whose results equal the composition's bit for bit and which keep no
+    relu(x) for backward. Everything else runs the composition: CPU tensors, other
+    dtypes and shapes, ADANET_NATIVE_CONV=0 and ADANET_FUSED_RELU_DW=0.
+    ReLU is v > 0 ? v : +0; NaN inputs are outside the bit-for-bit contract.
+    """
+    if relu_depthwise_supported(x, weight, stride, padding):
+        return _ReluDepthwiseFn.apply(x, weight.contiguous(), stride, padding)
+    return depthwise_conv2d(F.relu(x), weight, stride, padding)
+
+
 def _fused_sepconv_enabled() -> bool:
     import os
     return os.environ.get("ADANET_FUSED_SEPCONV", "1") != "0"

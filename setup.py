@@ -34,6 +34,7 @@ SRC = [
     "adanet_amd/csrc/depthwise.hip",
     "adanet_amd/csrc/sepconv_infer.hip",
     "adanet_amd/csrc/factred.hip",
+    "adanet_amd/csrc/relu_depthwise.hip",
 ]
 
 def _version():
