@@ -143,6 +143,13 @@ void relu_depthwise_bwd(const at::Tensor& x, const at::Tensor& dy,
                         const c10::optional<at::Tensor>& dx,
                         const c10::optional<at::Tensor>& dw, int64_t stride,
                         int64_t pad);
+bool relu_pointwise_supported(int64_t Ci, int64_t Co, int64_t H, int64_t W);
+void relu_pointwise_fwd(const at::Tensor& x, const at::Tensor& w,
+                        at::Tensor& y);
+void relu_pointwise_bwd_dx(const at::Tensor& dy, const at::Tensor& x,
+                           const at::Tensor& w, at::Tensor& dx);
+void relu_conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3,
+                     at::Tensor& dw);
 void argmax_correct(const at::Tensor& logits, const at::Tensor& labels,
                     const c10::optional<at::Tensor>& pred, at::Tensor& correct);
 void im2col_bf16(const at::Tensor& x, at::Tensor& out, int64_t K,
@@ -297,4 +304,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "half and leaves it untouched",
         py::arg("x"), py::arg("dy"), py::arg("w"), py::arg("dx"),
         py::arg("dw"), py::arg("stride"), py::arg("pad"));
+  m.def("relu_pointwise_supported", &relu_pointwise_supported,
+        "whether the fused relu -> 1x1 conv kernels take the shape",
+        py::arg("Ci"), py::arg("Co"), py::arg("H"), py::arg("W"));
+  m.def("relu_pointwise_fwd", &relu_pointwise_fwd,
+        "y[b] = w @ relu(x[b]), relu(x) never written to memory",
+        py::arg("x"), py::arg("w"), py::arg("y"));
+  m.def("relu_pointwise_bwd_dx", &relu_pointwise_bwd_dx,
+        "dx[b] = x[b] > 0 ? w^T @ dy[b] : 0, every dx element written once",
+        py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("dx"));
+  m.def("relu_conv1x1_dw", &relu_conv1x1_dw,
+        "conv1x1_dw on relu(x3), the clamp applied to the staged fragments",
+        py::arg("dy3"), py::arg("x3"), py::arg("dw"));
 }

@@ -281,7 +281,13 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_wave_kernel(
 // offset per operand plus its hw, and advances them by adds only: 32 k
 // forward is (32 / HW) whole images plus 32 % HW, with one conditional
 // wrap into the next image. No divide in the K loop.
-template <bool SPLITK>
+//
+// RELU: the weight gradient of a pointwise conv behind a ReLU
+// (relu_conv1x1_dw): x is staged as it lies and every x fragment is clamped
+// on its packed halves after the LDS read, so relu(x) need not exist in
+// memory. Partition, K order and epilogue are untouched: the result is
+// conv1x1_dw's on relu(x), bit for bit.
+template <bool SPLITK, bool RELU = false>
 __global__ __launch_bounds__(256, 6) void conv1x1_dw_kernel(
     const bf16_t* __restrict__ DY, const bf16_t* __restrict__ X,
     bf16_t* __restrict__ DW, float* __restrict__ C32, int Co, int Ci, int HW,
@@ -371,6 +377,16 @@ __global__ __launch_bounds__(256, 6) void conv1x1_dw_kernel(
     for (int f = 0; f < 2; ++f) {
       a[f] = *(const frag_ab*)&As[buf][(arow + f * 16) * KSTEP + kofs];
       b[f] = *(const frag_ab*)&Bs[buf][(brow + f * 16) * KSTEP + kofs];
+      if (RELU) {
+        // clear every bf16 half whose sign bit is set
+        i32x4 q = __builtin_bit_cast(i32x4, b[f]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const unsigned h = (unsigned)q[e];
+          q[e] = (int)(h & ~(((h >> 15) & 0x00010001u) * 0xffffu));
+        }
+        b[f] = __builtin_bit_cast(frag_ab, q);
+      }
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -715,7 +731,9 @@ void gemm_nt_bf16(const at::Tensor& A, const at::Tensor& B, at::Tensor& C,
 // HW % 8 == 0 and (B*HW) % 32 == 0 (callers take the permute-copy +
 // gemm_nt_bf16 path otherwise). The K partition is gemm_nt_bf16's, so where
 // that takes its split-K branch for (Co, Ci, B*HW) the two agree bit for bit.
-void conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3, at::Tensor& dw) {
+template <bool RELU>
+static void conv1x1_dw_launch(const at::Tensor& dy3, const at::Tensor& x3,
+                              at::Tensor& dw) {
   TORCH_CHECK(dy3.is_cuda() && x3.is_cuda() && dw.is_cuda(),
               "conv1x1_dw: need GPU tensors");
   TORCH_CHECK(dy3.get_device() == x3.get_device() &&
@@ -751,19 +769,31 @@ void conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3, at::Tensor& dw) {
   bf16_t* out = (bf16_t*)dw.data_ptr();
   const int lddw = (int)dw.stride(0);
   if (ksplit == 1) {
-    hipLaunchKernelGGL((conv1x1_dw_kernel<false>), dim3(mt * nt), dim3(256),
-                       0, stream.stream(), dy, x, out, nullptr, (int)Co,
-                       (int)Ci, (int)HW, K, lddw, mt, nt, 1);
+    hipLaunchKernelGGL((conv1x1_dw_kernel<false, RELU>), dim3(mt * nt),
+                       dim3(256), 0, stream.stream(), dy, x, out, nullptr,
+                       (int)Co, (int)Ci, (int)HW, K, lddw, mt, nt, 1);
   } else {
     auto C32 = at::empty({ksplit, Co, Ci}, dy3.options().dtype(at::kFloat));
-    hipLaunchKernelGGL((conv1x1_dw_kernel<true>), dim3(mt * nt * ksplit),
-                       dim3(256), 0, stream.stream(), dy, x, out,
+    hipLaunchKernelGGL((conv1x1_dw_kernel<true, RELU>),
+                       dim3(mt * nt * ksplit), dim3(256), 0, stream.stream(),
+                       dy, x, out,
                        C32.data_ptr<float>(), (int)Co, (int)Ci, (int)HW, K,
                        lddw, mt, nt, ksplit);
     launch_splitk_epilogue(C32.data_ptr<float>(), nullptr, out, (int)Co,
                            (int)Ci, lddw, 0, ksplit, stream.stream());
   }
   HIP_CHECK_KERNEL();
+}
+
+void conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3, at::Tensor& dw) {
+  conv1x1_dw_launch<false>(dy3, x3, dw);
+}
+
+// conv1x1_dw(dy3, relu(x3), dw) without relu(x3) in memory: same contract,
+// same partition, same bits for finite x3.
+void relu_conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3,
+                     at::Tensor& dw) {
+  conv1x1_dw_launch<true>(dy3, x3, dw);
 }
 
 // Tuning probe: dispatch a specific tile/occupancy/K-step variant so a

@@ -140,6 +140,15 @@ class ReluConvBN(nn.Module):
         if isinstance(self.op[1], HipConv1x1) and _fused_infer(self, x):
             return sepconv_bn_infer(x, None, self.op[1].weight,
                                     self.op[2].bn)
+        from adanet_amd.ops.conv import relu_conv1x1, relu_conv1x1_supported
+        conv = self.op[1]
+        if isinstance(conv, HipConv1x1) and conv.bias is None \
+                and relu_conv1x1_supported(x, conv.weight):
+            # training: the ReLU rides inside the pointwise kernels
+            # (csrc/relu_pointwise.hip, bit-identical to the modules), so no
+            # relu(x) of the wide adaptor input is kept for backward.
+            # self.op[0] stays in the Sequential for the state-dict indices.
+            return self.op[2](relu_conv1x1(x, conv.weight))
         return self.op(x)
 
 

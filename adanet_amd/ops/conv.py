@@ -335,6 +335,96 @@ def _bf16_dense(t: torch.Tensor) -> bool:
             and t.data_ptr() % 16 == 0)
 
 
+def _fused_relu_pw_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_FUSED_RELU_PW", "1") != "0"
+
+
+def _relu_pw_pays(ci: int, co: int, hw: int) -> bool:
+    """The part of the kernels' class where both fused directions measured
+    no slower than the chain (BENCHMARKS.md, "Fused ReLU -> pointwise"):
+    planes of at least 256 pixels (16x16 and 32x32, Ci 96 to 320), and
+    smaller planes up to Ci = 96 (8x8, 96 -> 32). On 8x8 planes with
+    Ci = 640 a block walks 20 chunks with one 64-pixel tile's worth of loads
+    in flight, and one direction lost to the chain by more than the spread
+    (640 -> 128 forward 35.1 us against 27.3, 640 -> 64 backward 52.7
+    against 46.2), so those shapes keep the chain."""
+    return hw >= 256 or ci <= 96
+
+
+def relu_conv1x1_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """Whether `relu_conv1x1` runs these arguments on the fused kernels
+    (csrc/relu_pointwise.hip) rather than on relu then `conv1x1`: the
+    kernels must take them and must have measured no slower than the chain
+    at that size (`_relu_pw_pays`)."""
+    if x.dim() != 4 or weight.dim() not in (2, 4) or not _native_enabled() \
+            or not _fused_relu_pw_enabled() or not _bf16_dense(x) \
+            or not _bf16_dense(weight) or x.numel() == 0 \
+            or x.shape[0] > 65535 \
+            or weight.numel() != weight.shape[0] * x.shape[1]:
+        return False
+    _, ci, h, w = x.shape
+    co = weight.shape[0]
+    return _relu_pw_pays(ci, co, h * w) and _extension.require(
+    ).relu_pointwise_supported(ci, co, h, w)
+
+
+class _ReluConv1x1Fn(torch.autograd.Function):
+    """relu -> 1x1 conv on csrc/relu_pointwise.hip: one launch forward, one
+    for the masked dX, and conv1x1_dw's kernel with the clamp on its x
+    fragments for dW. Saves x and the weight only; relu(x) never exists in
+    memory."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        B, _, H, W = x.shape
+        y = torch.empty((B, weight.shape[0], H, W), device=x.device,
+                        dtype=torch.bfloat16)
+        _extension.require().relu_pointwise_fwd(x, weight, y)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _extension.require()
+        x, weight = ctx.saved_tensors
+        B, Ci, H, W = x.shape
+        dy = dy.contiguous()
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            ext.relu_pointwise_bwd_dx(dy, x, weight, dx)
+        if ctx.needs_input_grad[1]:
+            dy3 = dy.reshape(B, weight.shape[0], H * W)
+            if _dw_direct_enabled() and (B * H * W) % 32 == 0:
+                dw = torch.empty((weight.shape[0], Ci), device=x.device,
+                                 dtype=torch.bfloat16)
+                ext.relu_conv1x1_dw(dy3, x.reshape(B, Ci, H * W), dw)
+            else:
+                # the chain's copy path permutes its operands anyway
+                dw = _weight_grad(dy3, F.relu(x).reshape(B, Ci, H * W))
+            dw = dw.reshape(weight.shape)
+        return dx, dw
+
+
+def relu_conv1x1(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """conv1x1(relu(x), weight), weight [Co, Ci] or [Co, Ci, 1, 1], no
+    bias. Differentiable. Contiguous, 16-byte aligned bf16 GPU tensors with
+    Ci % 32 == 0, Co % 32 == 0, Co <= 128 and H*W % 8 == 0, at the sizes
+    where they measured no slower (`relu_conv1x1_supported`), run the fused
+    kernels, whose y, dx and dW equal the composition's bit for bit and
+    which keep no relu(x) for backward. Everything else runs the
+    composition: CPU tensors, other dtypes and shapes, ADANET_NATIVE_CONV=0
+    and ADANET_FUSED_RELU_PW=0. ReLU is v > 0 ? v : +0; NaN inputs are
+    outside the bit-for-bit contract.
+    """
+    if relu_conv1x1_supported(x, weight):
+        return _ReluConv1x1Fn.apply(x, weight)
+    return conv1x1(F.relu(x), weight)
+
+
 def sepconv_infer_supported(x: torch.Tensor,
                             dw_weight: Optional[torch.Tensor],
                             pw_weight: torch.Tensor, stride: int = 1,
