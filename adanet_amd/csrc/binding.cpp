@@ -143,6 +143,13 @@ void relu_depthwise_bwd(const at::Tensor& x, const at::Tensor& dy,
                         const c10::optional<at::Tensor>& dx,
                         const c10::optional<at::Tensor>& dw, int64_t stride,
                         int64_t pad);
+bool relu_depthwise_strip_supported(int64_t C, int64_t H, int64_t W,
+                                    int64_t KS, int64_t stride, int64_t pad);
+void relu_depthwise_strip_fwd(const at::Tensor& x, const at::Tensor& w,
+                              at::Tensor& y, int64_t stride, int64_t pad);
+void relu_depthwise_strip_bwd_dx(const at::Tensor& x, const at::Tensor& dy,
+                                 const at::Tensor& w, at::Tensor& dx,
+                                 int64_t stride, int64_t pad);
 bool relu_pointwise_supported(int64_t Ci, int64_t Co, int64_t H, int64_t W);
 void relu_pointwise_fwd(const at::Tensor& x, const at::Tensor& w,
                         at::Tensor& y);
@@ -304,6 +311,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "half and leaves it untouched",
         py::arg("x"), py::arg("dy"), py::arg("w"), py::arg("dx"),
         py::arg("dw"), py::arg("stride"), py::arg("pad"));
+  m.def("relu_depthwise_strip_supported", &relu_depthwise_strip_supported,
+        "whether the strip-tiled relu -> depthwise kernels take the shape",
+        py::arg("C"), py::arg("H"), py::arg("W"), py::arg("KS"),
+        py::arg("stride"), py::arg("pad"));
+  m.def("relu_depthwise_strip_fwd", &relu_depthwise_strip_fwd,
+        "y = depthwise(relu(x)) on the strip tiling",
+        py::arg("x"), py::arg("w"), py::arg("y"), py::arg("stride"),
+        py::arg("pad"));
+  m.def("relu_depthwise_strip_bwd_dx", &relu_depthwise_strip_bwd_dx,
+        "dx = x > 0 ? dX(dy) : +0 on the strip tiling, every dx element "
+        "written once",
+        py::arg("x"), py::arg("dy"), py::arg("w"), py::arg("dx"),
+        py::arg("stride"), py::arg("pad"));
   m.def("relu_pointwise_supported", &relu_pointwise_supported,
         "whether the fused relu -> 1x1 conv kernels take the shape",
         py::arg("Ci"), py::arg("Co"), py::arg("H"), py::arg("W"));

@@ -91,6 +91,29 @@ __device__ __forceinline__ void stage_span(bf16_t* dst, const bf16_t* src,
   }
 }
 
+// Block barrier of the ReLU-fused files (relu_depthwise.hip,
+// relu_depthwise_strip.hip): they are built without some target features,
+// and the runtime header's __syncthreads is not inlined into such code.
+__device__ __forceinline__ void rd_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// Zero each bf16 lane of a 32-bit word whose sign bit is set (-0 included).
+__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {
+  const uint32_t neg = (v >> 15) & 0x00010001u;  // 1 per negative lane
+  return v & ~(neg * 0xffffu);
+}
+
+__device__ __forceinline__ uint4 relu_bf16x8(uint4 v) {
+  v.x = relu_bf16x2(v.x);
+  v.y = relu_bf16x2(v.y);
+  v.z = relu_bf16x2(v.z);
+  v.w = relu_bf16x2(v.w);
+  return v;
+}
+
 // dw[c*KSQ+t] = sum over chunks of wsp[(chunk*C + c)*KSQ + t], in fixed
 // order, on `stream` (depthwise_dw_reduce_kernel; defined in depthwise.hip
 // so the kernel has one code object).

@@ -26,25 +26,6 @@
                              apply_to = function)
 #endif
 
-__device__ __forceinline__ void rd_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// Zero each bf16 lane of a 32-bit word whose sign bit is set (-0 included).
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {
-  const uint32_t neg = (v >> 15) & 0x00010001u;  // 1 per negative lane
-  return v & ~(neg * 0xffffu);
-}
-
-__device__ __forceinline__ uint4 relu_bf16x8(uint4 v) {
-  v.x = relu_bf16x2(v.x);
-  v.y = relu_bf16x2(v.y);
-  v.z = relu_bf16x2(v.z);
-  v.w = relu_bf16x2(v.w);
-  return v;
-}
 __device__ __forceinline__ bf16_t relu_bf16(bf16_t v) {
   return bf2f(v) > 0.f ? v : f2bf(0.f);
 }

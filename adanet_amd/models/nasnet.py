@@ -108,8 +108,9 @@ class SepConv(nn.Module):
                                      dw.stride, dw.padding)
             return x
         # training: the ReLU rides inside the depthwise kernels where they
-        # support the shape (csrc/relu_depthwise.hip, bit-identical to the
-        # two modules), so no relu(x) is kept for backward. self.op[0] and
+        # support the shape (csrc/relu_depthwise.hip on small planes,
+        # csrc/relu_depthwise_strip.hip on 16x16 and 32x32; bit-identical to
+        # the two modules), so no relu(x) is kept for backward. self.op[0] and
         # self.op[4] stay in the Sequential for the state-dict indices.
         from adanet_amd.ops.conv import relu_depthwise_conv2d
         for i in (0, 4):

@@ -309,19 +309,101 @@ class _ReluDepthwiseFn(torch.autograd.Function):
         return dx, dw, None, None
 
 
+def _relu_dw_strip_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_RELU_DW_STRIP", "1") != "0"
+
+
+def _relu_dw_strip_pays(h: int, w: int, k: int, stride: int) -> bool:
+    """The size classes where the strip forward and the strip backward (dX
+    plus the dW-only launch and its reduce) both measured no slower than the
+    chain (BENCHMARKS.md, "Strip-tiled ReLU -> depthwise"): planes of 256 to
+    1024 pixels, where every measured K and stride won both ways (32x32 with
+    3x3 and 5x5 at stride 1 and 5x5 at stride 2, 16x16 with 5x5 and 7x7 at
+    stride 1 and 7x7 at stride 2: forward 2.4 to 4.9 times faster, backward
+    1.14 to 2.2 times). Larger planes of the kernels' class were not
+    measured and keep the chain, as do the sizes that the one-launch
+    kernels take first (`_relu_dw_pays`)."""
+    return 256 <= h * w <= 1024 and not _relu_dw_pays(h, w, k)
+
+
+def relu_depthwise_strip_supported(x: torch.Tensor, weight: torch.Tensor,
+                                   stride: int = 1, padding: int = 0) -> bool:
+    """Whether `relu_depthwise_conv2d` runs these arguments on the
+    strip-tiled kernels (csrc/relu_depthwise_strip.hip): 16-byte aligned
+    contiguous bf16 GPU tensors of the kernels' class (K in {3, 5, 7},
+    stride 1 or 2, padding K // 2, W % 8 == 0, H*W <= 4096; stride 2: H even
+    and W % 16 == 0) at a size where they measured no slower than the chain
+    (`_relu_dw_strip_pays`), with ADANET_RELU_DW_STRIP not 0."""
+    if x.dim() != 4 or weight.dim() != 4 or not _native_enabled() \
+            or not _fused_relu_dw_enabled() or not _relu_dw_strip_enabled() \
+            or not _bf16_dense(x) or not _bf16_dense(weight) \
+            or weight.shape[0] != x.shape[1] or weight.shape[1] != 1 \
+            or weight.shape[2] != weight.shape[3] or x.numel() == 0:
+        return False
+    _, c, h, w = x.shape
+    k = weight.shape[-1]
+    return _relu_dw_strip_pays(h, w, k, stride) and _extension.require(
+    ).relu_depthwise_strip_supported(c, h, w, k, stride, padding)
+
+
+class _ReluDepthwiseStripFn(torch.autograd.Function):
+    """relu -> depthwise KxK on csrc/relu_depthwise_strip.hip: one launch
+    forward, one for the masked dX, and relu_depthwise_bwd's dW-only launch
+    plus the slot sum. Saves x and the weight only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, pad):
+        B, C, H, W = x.shape
+        KS = weight.shape[-1]
+        y = torch.empty((B, C, (H + 2 * pad - KS) // stride + 1,
+                         (W + 2 * pad - KS) // stride + 1), device=x.device,
+                        dtype=torch.bfloat16)
+        _extension.require().relu_depthwise_strip_fwd(x, weight, y, stride,
+                                                      pad)
+        ctx.save_for_backward(x, weight)
+        ctx.stride, ctx.pad = stride, pad
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = _extension.require()
+        x, weight = ctx.saved_tensors
+        dy = dy.contiguous()
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            ext.relu_depthwise_strip_bwd_dx(x, dy, weight, dx, ctx.stride,
+                                            ctx.pad)
+        if ctx.needs_input_grad[1]:
+            dwf = torch.empty(weight.numel(), device=x.device,
+                              dtype=torch.float32)
+            ext.relu_depthwise_bwd(x, dy, weight, None, dwf, ctx.stride,
+                                   ctx.pad)
+            dw = dwf.reshape(weight.shape).to(weight.dtype)
+        return dx, dw, None, None
+
+
 def relu_depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor,
                           stride: int = 1, padding: int = 0) -> torch.Tensor:
     """depthwise_conv2d(relu(x), weight, stride, padding), weight
     [C, 1, K, K]. Differentiable. Contiguous bf16 GPU tensors with K in
-    {3, 5, 7}, stride 1 or 2 and H*W*K*K <= 2304, the sizes at which they
-    measured no slower (`relu_depthwise_supported`), run the fused kernels,
-    whose results equal the composition's bit for bit and which keep no
-    relu(x) for backward. Everything else runs the composition: CPU tensors, other
-    dtypes and shapes, ADANET_NATIVE_CONV=0 and ADANET_FUSED_RELU_DW=0.
+    {3, 5, 7} and stride 1 or 2 run fused kernels at the sizes where those
+    measured no slower: the one-launch kernels where H*W*K*K <= 2304
+    (`relu_depthwise_supported`), the strip-tiled kernels on larger planes
+    (`relu_depthwise_strip_supported`). Their results equal the
+    composition's bit for bit and they keep no relu(x) for backward.
+    Everything else runs the composition: CPU tensors, other dtypes and
+    shapes, ADANET_NATIVE_CONV=0 and ADANET_FUSED_RELU_DW=0;
+    ADANET_RELU_DW_STRIP=0 turns off the strip-tiled branch alone.
     ReLU is v > 0 ? v : +0; NaN inputs are outside the bit-for-bit contract.
     """
     if relu_depthwise_supported(x, weight, stride, padding):
         return _ReluDepthwiseFn.apply(x, weight.contiguous(), stride, padding)
+    if relu_depthwise_strip_supported(x, weight, stride, padding):
+        return _ReluDepthwiseStripFn.apply(x, weight, stride, padding)
     return depthwise_conv2d(F.relu(x), weight, stride, padding)
 
 

@@ -3,6 +3,9 @@
 forward   relu_depthwise_fwd           vs  torch.relu + depthwise_fwd
 backward  relu_depthwise_bwd (dx, dw)  vs  depthwise_bwd_dw + depthwise_bwd_dx
                                            + threshold_backward
+and, where the strip-tiled kernels take the shape, against both
+strip     relu_depthwise_strip_fwd;  relu_depthwise_strip_bwd_dx (strip_dx)
+          + relu_depthwise_bwd's dW-only launch and reduce (strip_dw)
 at the NASNet(filters=32) depthwise shapes of depthwise_bench.py. Each sample
 is one pass over a ring of buffer sets larger than the caches, timed with
 device events; fused and chain samples alternate, and the medians and the
@@ -109,19 +112,44 @@ def main():
             ext.depthwise_bwd_dx(s["dy"], s["w"], s["dr"], stride, pad)
             s["dx2"] = torch.ops.aten.threshold_backward(s["dr"], s["r"], 0)
 
+        def fwd_strip(s):
+            ext.relu_depthwise_strip_fwd(s["x"], s["w"], s["y"], stride, pad)
+
+        def bwd_strip_dx(s):
+            ext.relu_depthwise_strip_bwd_dx(s["x"], s["dy"], s["w"], s["dx"],
+                                            stride, pad)
+
+        def bwd_strip_dw(s):
+            ext.relu_depthwise_bwd(s["x"], s["dy"], s["w"], None, s["dw"],
+                                   stride, pad)
+
+        def bwd_strip(s):
+            bwd_strip_dx(s)
+            bwd_strip_dw(s)
+
         s = sets[0]
         for f in (fwd_fused, fwd_chain, bwd_fused, bwd_chain):
             f(s)
         same = bool(torch.equal(s["y"], s["y2"]) and
                     torch.equal(s["dx"], s["dx2"]) and
                     torch.equal(s["dw"], s["dw2"]))
+        fwd = {"fused": fwd_fused, "chain": fwd_chain}
+        bwd = {"fused": bwd_fused, "split": bwd_split, "chain": bwd_chain}
+        if ext.relu_depthwise_strip_supported(C, H, H, KS, stride, pad):
+            for t in (s["y"], s["dx"], s["dw"]):
+                t.fill_(3.0)
+            fwd_strip(s)
+            bwd_strip(s)
+            same = bool(same and torch.equal(s["y"], s["y2"]) and
+                        torch.equal(s["dx"], s["dx2"]) and
+                        torch.equal(s["dw"], s["dw2"]))
+            fwd["strip"] = fwd_strip
+            bwd.update(strip=bwd_strip, strip_dx=bwd_strip_dx,
+                       strip_dw=bwd_strip_dw)
         row = {"shape": [B, C, H, KS, stride], "bit_identical": same,
                "ring": len(sets),
-               "fwd": _compare({"fused": fwd_fused, "chain": fwd_chain},
-                               sets, args.samples, args.warmup),
-               "bwd": _compare({"fused": bwd_fused, "split": bwd_split,
-                                "chain": bwd_chain}, sets, args.samples,
-                               args.warmup)}
+               "fwd": _compare(fwd, sets, args.samples, args.warmup),
+               "bwd": _compare(bwd, sets, args.samples, args.warmup)}
         print(json.dumps(row), flush=True)
         rows.append(row)
         del sets

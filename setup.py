@@ -35,6 +35,7 @@ SRC = [
     "adanet_amd/csrc/sepconv_infer.hip",
     "adanet_amd/csrc/factred.hip",
     "adanet_amd/csrc/relu_depthwise.hip",
+    "adanet_amd/csrc/relu_depthwise_strip.hip",
     "adanet_amd/csrc/relu_pointwise.hip",
 ]
 
