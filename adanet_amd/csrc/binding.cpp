@@ -150,6 +150,8 @@ void relu_depthwise_strip_fwd(const at::Tensor& x, const at::Tensor& w,
 void relu_depthwise_strip_bwd_dx(const at::Tensor& x, const at::Tensor& dy,
                                  const at::Tensor& w, at::Tensor& dx,
                                  int64_t stride, int64_t pad);
+void relu_depthwise_strip_bwd_dw(const at::Tensor& x, const at::Tensor& dy,
+                                 at::Tensor& dw, int64_t stride, int64_t pad);
 bool relu_pointwise_supported(int64_t Ci, int64_t Co, int64_t H, int64_t W);
 void relu_pointwise_fwd(const at::Tensor& x, const at::Tensor& w,
                         at::Tensor& y);
@@ -324,6 +326,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "written once",
         py::arg("x"), py::arg("dy"), py::arg("w"), py::arg("dx"),
         py::arg("stride"), py::arg("pad"));
+  m.def("relu_depthwise_strip_bwd_dw", &relu_depthwise_strip_bwd_dw,
+        "fp32 dw[C*KS*KS] = dW(relu(x), dy) on the strip tiling, the bits "
+        "of relu_depthwise_bwd's dw",
+        py::arg("x"), py::arg("dy"), py::arg("dw"), py::arg("stride"),
+        py::arg("pad"));
   m.def("relu_pointwise_supported", &relu_pointwise_supported,
         "whether the fused relu -> 1x1 conv kernels take the shape",
         py::arg("Ci"), py::arg("Co"), py::arg("H"), py::arg("W"));

@@ -1,5 +1,6 @@
 // Tap loops, staging and argument checks shared by the depthwise kernels
-// (depthwise.hip) and the ReLU-fused ones (relu_depthwise.hip).
+// (depthwise.hip) and the ReLU-fused ones (relu_depthwise.hip,
+// relu_depthwise_strip.hip).
 #pragma once
 
 #include <torch/extension.h>
@@ -112,6 +113,35 @@ __device__ __forceinline__ uint4 relu_bf16x8(uint4 v) {
   v.z = relu_bf16x2(v.z);
   v.w = relu_bf16x2(v.w);
   return v;
+}
+
+__device__ __forceinline__ bf16_t relu_bf16(bf16_t v) {
+  return bf2f(v) > 0.f ? v : f2bf(0.f);
+}
+
+// Channel c's planes of images g .. g+ni-1 (px pixels each, C * px apart in
+// memory) into a dense LDS array, clamped in flight if RELU; by uint4 when
+// px is a multiple of 8.
+template <bool RELU>
+__device__ __forceinline__ void stage_planes(bf16_t* dst, const bf16_t* src,
+                                             int g, int ni, int C, int c,
+                                             int px) {
+  if ((px & 7) == 0) {
+    const int v = px >> 3;
+    for (int i = threadIdx.x; i < ni * v; i += 256) {
+      const int img = i / v;
+      uint4 q = ((const uint4*)(
+          src + ((int64_t)(g + img) * C + c) * px))[i - img * v];
+      if (RELU) q = relu_bf16x8(q);
+      ((uint4*)dst)[i] = q;
+    }
+  } else {
+    for (int i = threadIdx.x; i < ni * px; i += 256) {
+      const int img = i / px;
+      const bf16_t q = src[((int64_t)(g + img) * C + c) * px + (i - img * px)];
+      dst[i] = RELU ? relu_bf16(q) : q;
+    }
+  }
 }
 
 // dw[c*KSQ+t] = sum over chunks of wsp[(chunk*C + c)*KSQ + t], in fixed

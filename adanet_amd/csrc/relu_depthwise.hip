@@ -26,10 +26,6 @@
                              apply_to = function)
 #endif
 
-__device__ __forceinline__ bf16_t relu_bf16(bf16_t v) {
-  return bf2f(v) > 0.f ? v : f2bf(0.f);
-}
-
 // stage_span with the ReLU applied in flight: n pixels of whole images, by
 // uint4 when an image is a multiple of 8 pixels (every group then starts on
 // a 16-byte boundary).
@@ -87,30 +83,8 @@ __global__ __launch_bounds__(256) void relu_depthwise_fwd_kernel(
 }
 
 // --------------------------------------------------------------- backward
-// Channel c's planes of images g .. g+ni-1 (px pixels each, C * px apart in
-// memory) to or from a dense LDS array; by uint4 when px is a multiple of 8.
-template <bool RELU>
-__device__ __forceinline__ void stage_planes(bf16_t* dst, const bf16_t* src,
-                                             int g, int ni, int C, int c,
-                                             int px) {
-  if ((px & 7) == 0) {
-    const int v = px >> 3;
-    for (int i = threadIdx.x; i < ni * v; i += 256) {
-      const int img = i / v;
-      uint4 q = ((const uint4*)(
-          src + ((int64_t)(g + img) * C + c) * px))[i - img * v];
-      if (RELU) q = relu_bf16x8(q);
-      ((uint4*)dst)[i] = q;
-    }
-  } else {
-    for (int i = threadIdx.x; i < ni * px; i += 256) {
-      const int img = i / px;
-      const bf16_t q = src[((int64_t)(g + img) * C + c) * px + (i - img * px)];
-      dst[i] = RELU ? relu_bf16(q) : q;
-    }
-  }
-}
-
+// stage_planes (depthwise_common.h) in the other direction: a dense LDS
+// array to channel c's planes of images g .. g+ni-1.
 __device__ __forceinline__ void unstage_planes(bf16_t* dst, const bf16_t* src,
                                                int g, int ni, int C, int c,
                                                int px) {

@@ -3,7 +3,8 @@
 // issue and address arithmetic (one 2-byte LDS read per tap operand):
 //   relu_depthwise_strip_fwd     y  = depthwise(relu(x))
 //   relu_depthwise_strip_bwd_dx  dx = (x > 0) ? dX(dy) : +0
-// The weight gradient stays with relu_depthwise_bwd's dW-only launch.
+//   relu_depthwise_strip_bwd_dw  dw = dW(relu(x), dy), the bits of
+//                                relu_depthwise_bwd's dW (see the kernel)
 //
 // A 256-thread block stages a group of whole planes into LDS by 16-byte
 // chunks (x clamped in flight; dy as it is). A thread owns a strip: 8
@@ -36,6 +37,11 @@ constexpr int STRIP_LDS = 8192;  // staged pixels per block (16 KB)
 // rows but halves the strips per plane, and lost by 15 to 25 % on 16x16
 // planes and at stride 2; on 32x32 it won the forward by 2 %.
 constexpr int STRIP_ROWS = 2;
+// Outputs per strip of the dW kernel, whose lanes are 256 / S strips times K
+// tap rows: 4 is the narrowest that fits 256 lanes at K = 3 (192 lanes), 8
+// at K = 5 (160) and K = 7 (224); OW % 16 != 0 in the class rules out 16.
+// At K = 3, 8 (96 lanes) measured 18 to 21 % slower than 4 (BENCHMARKS.md).
+constexpr int strip_dw_width(int ks) { return ks == 3 ? 4 : 8; }
 }
 
 __device__ __forceinline__ float bf_lo(uint32_t v) {
@@ -231,6 +237,118 @@ __global__ __launch_bounds__(256) void relu_depthwise_strip_dx_kernel(
   }
 }
 
+// --------------------------------------------------------------------- dW
+// The dW phase of relu_depthwise_bwd_kernel, re-tiled without changing a bit.
+// Partition, staging, slot and block sum are that kernel's: grid (C, nchunks),
+// a block owns channel c and the images [b0, b1) of its chunk in groups of G,
+// stages the clamped x planes and the dy planes of a group, and sums 256
+// per-thread values per tap with block_reduce_sum into workspace slot
+// (chunk, c). There thread v adds, per tap, the products of the group's
+// outputs p = v, v + 256, ... in that order, groups ascending. Here those
+// 256 threads are virtual: a lane is (strip j, tap row kh) and owns the tap
+// row's KS sums of the S adjacent virtual threads S*j .. S*j + S - 1. In pass
+// k these are the outputs p = S*j + i + 256*k, S consecutive ow of one output
+// row (S divides OW and 256), so the lane reads the dy strip in one LDS read
+// and the x row ih = oh * STRIDE - pad + kh as whole units of S pixels, one
+// unit left of the strip's first input pixel: output i, tap kw is window
+// element S + STRIDE * i - pad + kw. Every (virtual thread, tap) sum sees its
+// terms in the order above; a column outside the plane, which that kernel
+// skips, meets a zero here, and adding +-0 to a sum that started at +0
+// leaves its bits alone (finite inputs). A row outside the plane is skipped
+// as there. At the end the sums go through LDS to thread v = virtual thread
+// v, 16 taps per round over the staging array, and into the same
+// block_reduce_sum on the same lane layout.
+template <int KS, int STRIDE, int S>
+__global__ __launch_bounds__(256) void relu_depthwise_strip_dw_kernel(
+    const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+    float* __restrict__ wsp, int B, int C, int H, int W, int OH, int OW,
+    int b_per_chunk, int G) {
+  constexpr int PAD = KS / 2, KSQ = KS * KS;
+  constexpr int NS = 256 / S;  // strips per pass
+  constexpr int NU = (S + STRIDE * (S - 1) - PAD + KS - 1) / S + 1;
+  constexpr int RT = STRIP_LDS * 2 / (256 * 4);  // taps per hand-over round
+  static_assert((S == 4 || S == 8) && NS * KS <= 256 && S >= PAD, "lanes");
+  // G * H * W <= 4096 and G * OH * OW <= 4096 (host)
+  __shared__ __align__(16) bf16_t lds[STRIP_LDS];
+  bf16_t* xs = lds;
+  bf16_t* ds = lds + STRIP_LDS / 2;
+  const int c = blockIdx.x;
+  const int b0 = blockIdx.y * b_per_chunk;
+  const int b1 = min(B, b0 + b_per_chunk);
+  const int ipx = H * W, opx = OH * OW;
+  const int kh = threadIdx.x / NS, j = threadIdx.x - kh * NS;
+  const bool lane = kh < KS;  // the rest only stages
+  // (img, oh, ow) of the strip's first output S*j, and of a step of 256
+  // outputs: three digits that advance with one carry each, no division
+  // per pass
+  const int img0 = S * j / opx, rem0 = S * j - img0 * opx;
+  const int oh0 = rem0 / OW, ow0 = rem0 - oh0 * OW;
+  const int dimg = 256 / opx, drem = 256 - dimg * opx;
+  const int doh = drem / OW, dow = drem - doh * OW;
+  float acc[S][KS];
+#pragma unroll
+  for (int i = 0; i < S; ++i)
+#pragma unroll
+    for (int kw = 0; kw < KS; ++kw) acc[i][kw] = 0.f;
+  for (int g = b0; g < b1; g += G) {
+    const int ni = min(G, b1 - g);
+    stage_planes<true>(xs, x, g, ni, C, c, ipx);
+    stage_planes<false>(ds, dy, g, ni, C, c, opx);
+    rd_sync();
+    if (lane) {
+      int img = img0, oh = oh0, ow = ow0;
+      // S divides opx, so a strip is inside the group or outside it
+      for (int p = S * j; p < ni * opx; p += 256) {
+        const int ih = oh * STRIDE - PAD + kh;
+        if (ih >= 0 && ih < H) {
+          float d[S], win[S * NU];
+          load_window<S, 1>(d, ds, p / S, STRIP_LDS / 2 / S);
+          load_window<S, NU>(win, xs + img * ipx + ih * W,
+                             STRIDE * (ow / S) - 1, W / S);
+#pragma unroll
+          for (int i = 0; i < S; ++i)
+#pragma unroll
+            for (int kw = 0; kw < KS; ++kw)
+              acc[i][kw] += d[i] * win[S + STRIDE * i - PAD + kw];
+        }
+        ow += dow;
+        if (ow >= OW) ow -= OW, ++oh;
+        oh += doh;
+        if (oh >= OH) oh -= OH, ++img;
+        img += dimg;
+      }
+    }
+    rd_sync();
+  }
+  // hand-over: red[tap of the round][virtual thread] over the staging array
+  // (the group loop ended on a barrier)
+  float* red = (float*)lds;
+  float out[KSQ];
+#pragma unroll
+  for (int r0 = 0; r0 < KSQ; r0 += RT) {
+    if (lane) {
+#pragma unroll
+      for (int kw = 0; kw < KS; ++kw) {
+        const int t = kh * KS + kw - r0;
+        if (t < 0 || t >= RT) continue;
+#pragma unroll
+        for (int q = 0; q < S; q += 4)
+          *(float4*)(red + t * 256 + S * j + q) =
+              make_float4(acc[q][kw], acc[q + 1][kw], acc[q + 2][kw],
+                          acc[q + 3][kw]);
+      }
+    }
+    rd_sync();
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+      if (r0 + t < KSQ) out[r0 + t] = red[t * 256 + threadIdx.x];
+    rd_sync();
+  }
+  float* slot = wsp + ((int64_t)blockIdx.y * C + c) * KSQ;
+  block_reduce_sum(
+      out, [&](int t, float v) { slot[t] = v; }, [] { rd_sync(); });
+}
+
 // ------------------------------------------------------------------- host
 namespace {
 
@@ -244,10 +362,9 @@ bool strip_shape_ok(int64_t C, int64_t H, int64_t W, int64_t KS,
 }
 
 DwShape check_strip(const at::Tensor& x, const char* xname,
-                    const at::Tensor& y, const char* yname,
-                    const at::Tensor& w, int64_t stride, int64_t pad) {
-  check_bf16(w, "w");
-  const DwShape s = check_images(x, xname, y, yname, w.numel(), stride, pad);
+                    const at::Tensor& y, const char* yname, int64_t taps,
+                    int64_t stride, int64_t pad) {
+  const DwShape s = check_images(x, xname, y, yname, taps, stride, pad);
   TORCH_CHECK(strip_shape_ok(s.C, s.H, s.W, s.KS, stride, pad),
               "relu_depthwise_strip: unsupported shape (KS in {3,5,7}, "
               "stride in {1,2}, pad == KS/2, W%8==0, H*W<=4096; stride 2: H "
@@ -255,10 +372,19 @@ DwShape check_strip(const at::Tensor& x, const char* xname,
               " stride=", stride, " pad=", pad);
   TORCH_CHECK((int64_t)s.B * s.C < (1LL << 31),
               "relu_depthwise_strip: B*C must stay below 2^31");
-  for (const at::Tensor* t : {&x, &y, &w})
+  for (const at::Tensor* t : {&x, &y})
     TORCH_CHECK((uintptr_t)t->data_ptr() % 16 == 0,
                 "relu_depthwise_strip: tensors must be 16-byte aligned");
   return s;
+}
+
+DwShape check_strip(const at::Tensor& x, const char* xname,
+                    const at::Tensor& y, const char* yname,
+                    const at::Tensor& w, int64_t stride, int64_t pad) {
+  check_bf16(w, "w");
+  TORCH_CHECK((uintptr_t)w.data_ptr() % 16 == 0,
+              "relu_depthwise_strip: tensors must be 16-byte aligned");
+  return check_strip(x, xname, y, yname, w.numel(), stride, pad);
 }
 
 // Planes per block: enough strips for the 256 threads, within the LDS array.
@@ -316,6 +442,42 @@ void relu_depthwise_strip_bwd_dx(const at::Tensor& x, const at::Tensor& dy,
           s.OH, s.OW, P, bc);
     });
   });
+  HIP_CHECK_KERNEL();
+}
+
+void relu_depthwise_strip_bwd_dw(const at::Tensor& x, const at::Tensor& dy,
+                                 at::Tensor& dw, int64_t stride,
+                                 int64_t pad) {
+  TORCH_CHECK(dw.is_cuda() && dw.is_contiguous() &&
+                  dw.scalar_type() == at::kFloat,
+              "relu_depthwise_strip: dw must be a contiguous fp32 CUDA "
+              "tensor of C*KS*KS elements");
+  const DwShape s = check_strip(x, "x", dy, "dy", dw.numel(), stride, pad);
+  // relu_depthwise_bwd's partition (depthwise_bwd_dw's LDS tier): part of
+  // the bit contract
+  const int nchunks =
+      (int)std::max<int64_t>(1, std::min<int64_t>(1024 / s.C, s.B));
+  const int b_per_chunk = (s.B + nchunks - 1) / nchunks;
+  const int G = std::max(
+      1, std::min({STRIP_LDS / 2 / (s.H * s.W),
+                   STRIP_LDS / 2 / (s.OH * s.OW), s.B}));
+  const int ksq = s.KS * s.KS;
+  at::Tensor wsp = at::empty({nchunks, s.C, ksq}, dw.options());
+  auto stream = at::cuda::getCurrentCUDAStream().stream();
+  with_const<3, 5, 7>(s.KS, [&](auto ks) {
+    with_const<1, 2>((int)stride, [&](auto st) {
+      constexpr int K = decltype(ks)::value;
+      hipLaunchKernelGGL(
+          (relu_depthwise_strip_dw_kernel<K, decltype(st)::value,
+                                          strip_dw_width(K)>),
+          dim3((unsigned)s.C, (unsigned)nchunks), dim3(256), 0, stream,
+          (const bf16_t*)x.data_ptr(), (const bf16_t*)dy.data_ptr(),
+          wsp.data_ptr<float>(), s.B, s.C, s.H, s.W, s.OH, s.OW, b_per_chunk,
+          G);
+    });
+  });
+  launch_depthwise_dw_reduce(wsp.data_ptr<float>(), dw.data_ptr<float>(), s.C,
+                             ksq, nchunks, stream);
   HIP_CHECK_KERNEL();
 }
 

@@ -327,6 +327,24 @@ def _relu_dw_strip_pays(h: int, w: int, k: int, stride: int) -> bool:
     return 256 <= h * w <= 1024 and not _relu_dw_pays(h, w, k)
 
 
+def _relu_dw_strip_dw_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_RELU_DW_STRIP_DW", "1") != "0"
+
+
+def _relu_dw_strip_dw_pays(h: int, w: int, k: int, stride: int) -> bool:
+    """The size classes where `relu_depthwise_strip_bwd_dw` measured below
+    `relu_depthwise_bwd`'s dW-only launch and reduce by more than both
+    interquartile ranges (BENCHMARKS.md, "Strip-tiled dW"; us per call at
+    batch 256, old / new, every range at most 0.27): 32x32 with 5x5
+    113.6 / 57.3, 3x3 56.4 / 39.0, 5x5 at stride 2 44.6 / 34.8; 16x16 with
+    5x5 62.9 / 35.8, 3x3 32.0 / 23.1, 7x7 110.6 / 48.2, 7x7 at stride 2
+    46.2 / 34.7; 8x8 with 5x5 45.7 / 28.2. That is every measured K and
+    stride on planes of 64 to 1024 pixels; larger planes of the kernel's
+    class were not measured and keep the old kernel."""
+    return 64 <= h * w <= 1024
+
+
 def relu_depthwise_strip_supported(x: torch.Tensor, weight: torch.Tensor,
                                    stride: int = 1, padding: int = 0) -> bool:
     """Whether `relu_depthwise_conv2d` runs these arguments on the
@@ -349,8 +367,10 @@ def relu_depthwise_strip_supported(x: torch.Tensor, weight: torch.Tensor,
 
 class _ReluDepthwiseStripFn(torch.autograd.Function):
     """relu -> depthwise KxK on csrc/relu_depthwise_strip.hip: one launch
-    forward, one for the masked dX, and relu_depthwise_bwd's dW-only launch
-    plus the slot sum. Saves x and the weight only."""
+    forward, one for the masked dX, and one plus the slot sum for dW: the
+    strip-tiled one where it measured faster (`_relu_dw_strip_dw_pays`, with
+    ADANET_RELU_DW_STRIP_DW not 0), else relu_depthwise_bwd's dW-only
+    instance; the two give the same bits. Saves x and the weight only."""
 
     @staticmethod
     def forward(ctx, x, weight, stride, pad):
@@ -380,8 +400,13 @@ class _ReluDepthwiseStripFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dwf = torch.empty(weight.numel(), device=x.device,
                               dtype=torch.float32)
-            ext.relu_depthwise_bwd(x, dy, weight, None, dwf, ctx.stride,
-                                   ctx.pad)
+            if _relu_dw_strip_dw_enabled() and _relu_dw_strip_dw_pays(
+                    x.shape[2], x.shape[3], weight.shape[-1], ctx.stride):
+                ext.relu_depthwise_strip_bwd_dw(x, dy, dwf, ctx.stride,
+                                                ctx.pad)
+            else:
+                ext.relu_depthwise_bwd(x, dy, weight, None, dwf, ctx.stride,
+                                       ctx.pad)
             dw = dwf.reshape(weight.shape).to(weight.dtype)
         return dx, dw, None, None
 
@@ -397,7 +422,10 @@ def relu_depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor,
     composition's bit for bit and they keep no relu(x) for backward.
     Everything else runs the composition: CPU tensors, other dtypes and
     shapes, ADANET_NATIVE_CONV=0 and ADANET_FUSED_RELU_DW=0;
-    ADANET_RELU_DW_STRIP=0 turns off the strip-tiled branch alone.
+    ADANET_RELU_DW_STRIP=0 turns off the strip-tiled branch alone, and
+    ADANET_RELU_DW_STRIP_DW=0 only its strip-tiled weight gradient, which
+    then comes from the one-launch kernel's dW-only instance with the same
+    bits.
     ReLU is v > 0 ? v : +0; NaN inputs are outside the bit-for-bit contract.
     """
     if relu_depthwise_supported(x, weight, stride, padding):

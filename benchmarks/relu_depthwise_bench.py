@@ -5,7 +5,8 @@ backward  relu_depthwise_bwd (dx, dw)  vs  depthwise_bwd_dw + depthwise_bwd_dx
                                            + threshold_backward
 and, where the strip-tiled kernels take the shape, against both
 strip     relu_depthwise_strip_fwd;  relu_depthwise_strip_bwd_dx (strip_dx)
-          + relu_depthwise_bwd's dW-only launch and reduce (strip_dw)
+          + relu_depthwise_bwd's dW-only launch and reduce (strip_dw),
+          and relu_depthwise_strip_bwd_dw in its place (strip_dw_new)
 at the NASNet(filters=32) depthwise shapes of depthwise_bench.py. Each sample
 is one pass over a ring of buffer sets larger than the caches, timed with
 device events; fused and chain samples alternate, and the medians and the
@@ -123,6 +124,10 @@ def main():
             ext.relu_depthwise_bwd(s["x"], s["dy"], s["w"], None, s["dw"],
                                    stride, pad)
 
+        def bwd_strip_dw_new(s):
+            ext.relu_depthwise_strip_bwd_dw(s["x"], s["dy"], s["dw"], stride,
+                                            pad)
+
         def bwd_strip(s):
             bwd_strip_dx(s)
             bwd_strip_dw(s)
@@ -143,9 +148,12 @@ def main():
             same = bool(same and torch.equal(s["y"], s["y2"]) and
                         torch.equal(s["dx"], s["dx2"]) and
                         torch.equal(s["dw"], s["dw2"]))
+            s["dw"].fill_(3.0)
+            bwd_strip_dw_new(s)
+            same = bool(same and torch.equal(s["dw"], s["dw2"]))
             fwd["strip"] = fwd_strip
             bwd.update(strip=bwd_strip, strip_dx=bwd_strip_dx,
-                       strip_dw=bwd_strip_dw)
+                       strip_dw=bwd_strip_dw, strip_dw_new=bwd_strip_dw_new)
         row = {"shape": [B, C, H, KS, stride], "bit_identical": same,
                "ring": len(sets),
                "fwd": _compare(fwd, sets, args.samples, args.warmup),
