@@ -159,6 +159,10 @@ void relu_pointwise_bwd_dx(const at::Tensor& dy, const at::Tensor& x,
                            const at::Tensor& w, at::Tensor& dx);
 void relu_conv1x1_dw(const at::Tensor& dy3, const at::Tensor& x3,
                      at::Tensor& dw);
+void conv1x1_ragged_fwd(const at::Tensor& x3, const at::Tensor& w,
+                        at::Tensor& y3);
+void conv1x1_ragged_dx(const at::Tensor& dy3, const at::Tensor& w,
+                       at::Tensor& dx3);
 void argmax_correct(const at::Tensor& logits, const at::Tensor& labels,
                     const c10::optional<at::Tensor>& pred, at::Tensor& correct);
 void im2col_bf16(const at::Tensor& x, at::Tensor& out, int64_t K,
@@ -343,4 +347,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_conv1x1_dw", &relu_conv1x1_dw,
         "conv1x1_dw on relu(x3), the clamp applied to the staged fragments",
         py::arg("dy3"), py::arg("x3"), py::arg("dw"));
+  m.def("conv1x1_ragged_fwd", &conv1x1_ragged_fwd,
+        "y3[b] = w @ x3[b] for any Ci, Co >= 1 (HW % 8 == 0), no padding",
+        py::arg("x3"), py::arg("w"), py::arg("y3"));
+  m.def("conv1x1_ragged_dx", &conv1x1_ragged_dx,
+        "dx3[b] = w^T @ dy3[b] for any Ci, Co >= 1 (HW % 8 == 0), no padding",
+        py::arg("dy3"), py::arg("w"), py::arg("dx3"));
 }

@@ -57,10 +57,12 @@ class Hparams:
     learn_mixture_weights: bool = False
     drop_path_keep: float = 0.9
     train_steps: int = 10000  # cosine horizon per iteration
-    #: round filter counts up to a multiple of this so the native conv
-    #: stack (batched-MFMA pointwise / unfold-GEMM adaptors, ops/conv.py)
-    #: engages; 1 = exact reference filter counts (library conv fallback
-    #: for unaligned channels). 32 is the GEMM alignment contract.
+    #: round filter counts up to a multiple of this. 1 = exact reference
+    #: filter counts: the pointwise convs then run the ragged-channel
+    #: kernels (csrc/conv1x1_ragged.hip), native and deterministic. 32 puts
+    #: them on the batched-MFMA GEMM and also engages the fused ReLU ->
+    #: pointwise, separable-conv inference and factorized-reduction
+    #: kernels, which keep a % 32 contract (ops/conv.py).
     channel_multiple: int = 1
 
 

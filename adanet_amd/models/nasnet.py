@@ -8,9 +8,10 @@ NASNet-A paper genotype, not translated. On the GPU in bf16 every op on the
 cell path runs on the in-tree gfx950 kernels: depthwise, pointwise (batched
 MFMA GEMM) and NxN convolutions, 3x3 pooling, BatchNorm with fp32 statistics
 under bf16 activations, and the fused cell combine (drop-path scale, add
-and channel concat in one launch, ops/combine.py); with filter counts that
-are multiples of 32 no MIOpen kernel is left on it (other counts take
-torch's conv for the pointwise/NxN convolutions, ops/conv.py). The
+and channel concat in one launch, ops/combine.py); no MIOpen kernel is left
+on it at any filter count (counts off the 32 grid run the ragged-channel
+pointwise kernels, csrc/conv1x1_ragged.hip, instead of the batched GEMM and
+the fused kernels that keep a % 32 contract, ops/conv.py). The
 classifier head and optimizers use the adanet_amd HIP kernels as well; on
 CPU the same modules fall back to plain torch.
 """

@@ -14,9 +14,15 @@ zero im2col and zero transpose copies for fwd/dX, and csrc/gemm.hip's
 conv1x1_dw reads dz and x for dW where they lie in [B, C, HW] (needs
 HW % 8 == 0 and B*HW % 32 == 0; other shapes, and ADANET_CONV_DW_DIRECT=0,
 make two channel-major permute copies and call gemm_nt_bf16 — bit-identical
-where that GEMM splits K). The fast path needs the GEMM alignment contract
-(Ci % 32 == 0, HW % 8 == 0); `conv1x1` falls back to torch's conv (MIOpen)
-otherwise, so arbitrary channel counts still work.
+where that GEMM splits K). gemm_tr_batched needs Ci % 32 == 0 and
+Co % 32 == 0. Every other channel count (the search space's own 10, 20, 30,
+42, ... filters) runs csrc/conv1x1_ragged.hip for forward and dX: the same
+accumulation order with the K tail zeroed in LDS and ragged output rows
+masked, no padded copies, bit-identical to the aligned path on zero-padded
+operands; its dW is conv1x1_dw, whose kernel masks both output axes. So the
+pointwise convs are native and run-to-run bit-identical at any channel
+count. What remains for torch's conv (MIOpen): HW % 8 != 0, non-bf16 or CPU
+tensors, ADANET_NATIVE_CONV=0, and ragged counts under ADANET_CONV_RAGGED=0.
 """
 
 from __future__ import annotations
@@ -35,11 +41,37 @@ def _native_enabled() -> bool:
     return os.environ.get("ADANET_NATIVE_CONV", "1") != "0"
 
 
-def _aligned(x: torch.Tensor, co: int, ci: int) -> bool:
+def _ragged_enabled() -> bool:
+    import os
+    return os.environ.get("ADANET_CONV_RAGGED", "1") != "0"
+
+
+def _on_grid(co: int, ci: int) -> bool:
+    """Both channel counts on the 32 grid: gemm_tr_batched's contract."""
+    return ci % 32 == 0 and co % 32 == 0
+
+
+def _ragged_ok(batch: int, hw: int, co: int, ci: int) -> bool:
+    """The host-side class of csrc/conv1x1_ragged.hip for activations
+    [batch, C, hw] and a [co, ci] weight (pointer alignment apart), with
+    ADANET_CONV_RAGGED not 0. The one place that mirrors the file's limits."""
+    return _ragged_enabled() and hw > 0 and hw % 8 == 0 \
+        and 1 <= batch <= 65535 and 1 <= min(co, ci) \
+        and max(co, ci) <= 65536
+
+
+def _conv1x1_native(x: torch.Tensor, co: int, ci: int) -> bool:
+    """Whether `_Conv1x1Fn` takes x [B, Ci, H, W] with a [Co, Ci] weight:
+    on the 32 grid through gemm_tr_batched, off it through
+    csrc/conv1x1_ragged.hip (ADANET_CONV_RAGGED=0 turns that off)."""
     if not x.is_cuda or x.dtype != torch.bfloat16 or not _native_enabled():
         return False
     hw = x.shape[2] * x.shape[3]
-    return ci % 32 == 0 and co % 32 == 0 and hw % 8 == 0 and x.is_contiguous()
+    if hw % 8 != 0 or not x.is_contiguous():
+        return False
+    if _on_grid(co, ci):
+        return True
+    return _ragged_ok(x.shape[0], hw, co, ci) and x.data_ptr() % 16 == 0
 
 
 def _dw_direct_enabled() -> bool:
@@ -94,7 +126,10 @@ class _Conv1x1Fn(torch.autograd.Function):
         y = torch.empty((B, Co, H * W), device=x.device, dtype=torch.bfloat16)
         # bias is per-OUTPUT-CHANNEL = per GEMM ROW; the GEMM epilogue's bias
         # is per-column, so add the bias afterwards (broadcast add).
-        ext.gemm_tr_batched(weight, x3, y, None, 0, 0, 1)
+        if _on_grid(Co, Ci):
+            ext.gemm_tr_batched(weight, x3, y, None, 0, 0, 1)
+        else:
+            ext.conv1x1_ragged_fwd(x3, weight, y)
         if bias is not None:
             y = y + bias.to(torch.bfloat16).reshape(1, Co, 1)
         ctx.save_for_backward(x, weight)
@@ -113,7 +148,12 @@ class _Conv1x1Fn(torch.autograd.Function):
             dx = torch.empty((B, Ci, H * W), device=x.device,
                              dtype=torch.bfloat16)
             # dX_b = W^T @ dz_b: both operands K(=Co)-major -> tt staging.
-            ext.gemm_tr_batched(weight, dy3, dx, None, 0, 1, 1)
+            if _on_grid(Co, Ci):
+                ext.gemm_tr_batched(weight, dy3, dx, None, 0, 1, 1)
+            else:
+                if dy3.data_ptr() % 16:
+                    dy3 = dy3.clone()
+                ext.conv1x1_ragged_dx(dy3, weight, dx)
             dx = dx.reshape(B, Ci, H, W)
         if ctx.needs_input_grad[1]:
             # dW[Co, Ci] = dz_all[Co, B*HW] @ x_all[Ci, B*HW]^T, read from
@@ -129,6 +169,9 @@ class HipConv1x1(nn.Module):
 
     Drop-in for ``nn.Conv2d(c_in, c_out, 1, bias=...)`` (stride 1). The
     weight keeps Conv2d's [Co, Ci, 1, 1] layout so state dicts interop.
+    Any channel counts are native for contiguous bf16 GPU input with
+    H*W % 8 == 0: multiples of 32 on gemm_tr_batched, the others on
+    csrc/conv1x1_ragged.hip (ADANET_CONV_RAGGED=0 sends those to torch).
     """
 
     def __init__(self, in_channels: int, out_channels: int, bias: bool = True,
@@ -146,16 +189,15 @@ class HipConv1x1(nn.Module):
 
     def forward(self, x):
         w2 = self.weight.reshape(self.out_channels, self.in_channels)
-        if _aligned(x, self.out_channels, self.in_channels) \
-                and w2.dtype == torch.bfloat16 \
-                and w2.stride(0) % 8 == 0 and w2.is_contiguous():
+        if _conv1x1_native(x, self.out_channels, self.in_channels) \
+                and w2.dtype == torch.bfloat16 and w2.is_contiguous():
             return _Conv1x1Fn.apply(x, w2, self.bias)
         return torch.nn.functional.conv2d(
             x, self.weight.to(x.dtype),
             self.bias.to(x.dtype) if self.bias is not None else None)
 
     def extra_repr(self):
-        return "in=%d, out=%d (native when C%%32==0)" % (
+        return "in=%d, out=%d (native when H*W%%8==0)" % (
             self.in_channels, self.out_channels)
 
 
@@ -165,7 +207,7 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor,
     if weight.dim() == 4:
         weight = weight.reshape(weight.shape[0], weight.shape[1])
     co, ci = weight.shape
-    if _aligned(x, co, ci) and weight.dtype == torch.bfloat16 \
+    if _conv1x1_native(x, co, ci) and weight.dtype == torch.bfloat16 \
             and weight.is_contiguous():
         return _Conv1x1Fn.apply(x, weight, bias)
     return torch.nn.functional.conv2d(
@@ -643,8 +685,10 @@ class HipConvNxN(nn.Module):
     profiles/conv_bench_r01.txt); expressing the conv as im2col (one
     torch.unfold copy, a few MB) + gemm_tr_batched keeps fwd/bwd on the
     MFMA path. The im2col K dim (Ci*K*K) is zero-padded to 32 inside the
-    padded weight, so ANY in-channel count works; requires Co % 32 == 0
-    (else torch fallback). Drop-in for
+    padded weight, so ANY in-channel count works. Co % 32 == 0 runs
+    gemm_tr_batched; any other Co runs csrc/conv1x1_ragged.hip when the
+    output plane has OH*OW % 8 == 0 (else, and with ADANET_CONV_RAGGED=0,
+    torch fallback). Drop-in for
     ``nn.Conv2d(ci, co, K, stride, padding, bias=...)``.
     """
 
@@ -668,7 +712,7 @@ class HipConvNxN(nn.Module):
         return conv_nxn(x, self.weight, self.bias, self.stride, self.padding)
 
     def extra_repr(self):
-        return "in=%d, out=%d, k=%d, s=%d (im2col+MFMA when Co%%32==0)" % (
+        return "in=%d, out=%d, k=%d, s=%d (im2col+MFMA)" % (
             self.in_channels, self.out_channels, self.kernel_size,
             self.stride)
 
@@ -680,10 +724,14 @@ def conv_nxn(x: torch.Tensor, weight: torch.Tensor,
     co, ci, K, _ = weight.shape
     ckk = ci * K * K
     ckk_pad = (ckk + 31) // 32 * 32
+    oh = (x.shape[2] + 2 * padding - K) // stride + 1
+    ow = (x.shape[3] + 2 * padding - K) // stride + 1
+    # Co off the 32 grid runs csrc/conv1x1_ragged.hip, which wants whole
+    # 16 B vectors per output row
     if (x.is_cuda and x.dtype == torch.bfloat16 and _native_enabled()
-            and weight.dtype == torch.bfloat16 and co % 32 == 0):
-        oh = (x.shape[2] + 2 * padding - K) // stride + 1
-        ow = (x.shape[3] + 2 * padding - K) // stride + 1
+            and weight.dtype == torch.bfloat16
+            and (co % 32 == 0
+                 or _ragged_ok(x.shape[0], oh * ow, co, ckk_pad))):
         # batched im2col with the 32-alignment zero-pad folded in
         # (torch's F.unfold is one im2col launch PER IMAGE).
         u = _Im2colFn.apply(x.contiguous(), K, stride, padding, ckk_pad,

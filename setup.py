@@ -37,6 +37,7 @@ SRC = [
     "adanet_amd/csrc/relu_depthwise.hip",
     "adanet_amd/csrc/relu_depthwise_strip.hip",
     "adanet_amd/csrc/relu_pointwise.hip",
+    "adanet_amd/csrc/conv1x1_ragged.hip",
 ]
 
 def _version():
